@@ -27,6 +27,21 @@ RMX_BENCH_BACKEND=gloo rehearses the multi-rank path on fewer GPUs than ranks (r
 
 Prints ONE JSON line (rank 0) with the driver's contract keys plus `roofline`, `cpu_baseline`, `parity` (the
 metric's CPU-ref parity rate) and `configs` (every BASELINE GPU config by the same protocol).
+
+Plain run and --full.  A plain `bench.py --gpus 1 --steps K --warmup W` does what `value` needs and no more: set-up,
+the spin-up, the reported windows of the headline config, the result line (the keys of what it did not measure are
+null; no detail file unless --detail names one).  Everything else above runs only with --full: the event windows and
+the roofline, the 500-step chain, the dispatch stamps, the fused rollout, the other BASELINE configs and random-start
+legs, the bandwidth regime, the CPU baseline and the parity samples, the detail file.
+
+Long windows.  A window's action rows stay in HBM; beyond --act-buf-mb (4 GiB) of them the buffer is cyclic (step g reads row
+g mod the buffer's rows) and the K steps run as consecutive rmx_step_seq calls (or graphs) over its contiguous runs,
+the report in the last one.  Reported windows are dropped from the front of the seed sequence (and the discarded
+first window with them) while they would take more than WINDOW_BUDGET_S together, so the last window's seed is fixed.
+
+--dump-outputs DIR writes what the last reported window's last step left a caller: the state columns, reward and
+the episode-statistics report as DIR/<name>.npy (integers as float64, exact; a fixed seeded sample of the envs,
+`env_index.npy`, when they would pass 64 MB).  Same arguments, same inputs: two builds compare array for array.
 """
 import argparse
 import gc
@@ -51,6 +66,9 @@ WORKLOADS = {
     5: "OfficeWorld map1, 65,536 envs/GPU x 3 agents, exp5 8-state RM + reward shaping, random actions",
 }
 WINDOW_SEEDS = (0, 1, 2, 0, 1)
+ACT_BUF_BYTES = 4 << 30  # a window's action rows in HBM; more steps than fit read the buffer cyclically
+WINDOW_BUDGET_S = 10.0  # the discarded and the reported windows together; fewer of them when K is that long
+DUMP_MAX_BYTES = 60 << 20  # --dump-outputs: all arrays together (the limit is 64 MB)
 BUILD = {}  # rmx_build_info() of the library this run loaded (run_rank)
 
 KERNEL_NAMES = {"fast": "rmx::step_fast_kernel", "fast_lpe": "rmx::step_fast_lpe_kernel",
@@ -62,6 +80,54 @@ def algorithmic_bytes_per_instance_step(A, shaping):
     reads pos_x,pos_y,rm_q,flags 16 + action 4 + ep_ret 4; writes the same 16 + reward 4 + ep_ret 4;
     per env t r/w 8 + env_done 1 (shared by A agents)."""
     return 48.0 + 9.0 / A + (4.0 if shaping else 0.0)
+
+
+def act_segments(g0, n, rows):
+    """Steps g0 .. g0+n-1 of a window on a cyclic action buffer of `rows` rows (step g reads row g % rows): the
+    contiguous runs [(first row, steps)], in step order.  One run while the window fits the buffer."""
+    out = []
+    while n > 0:
+        r = g0 % rows
+        m = min(n, rows - r)
+        out.append((r, m))
+        g0, n = g0 + m, n - m
+    return out
+
+
+def window_plan(n_windows, window_s, budget_s=WINDOW_BUDGET_S):
+    """(the seeds of the reported windows, whether a first window is run and discarded): the nominal seed sequence
+    while a discarded and n_windows reported windows of window_s seconds fit budget_s, else its tail (the last
+    window's seed never changes), at least one window, the discarded one only beside two more."""
+    seeds = [WINDOW_SEEDS[w % len(WINDOW_SEEDS)] for w in range(n_windows)]
+    fit = int(budget_s / max(window_s, 1e-9))
+    return seeds[-max(1, min(n_windows, fit - 1)):], fit >= 2
+
+
+def step_outputs(env, report, max_bytes=DUMP_MAX_BYTES):
+    """What a caller holds after a step, as host arrays for --dump-outputs: the state columns, reward (and shaping)
+    and the episode-statistics report; integer columns as float64 (exact), the rest float32.  More than max_bytes:
+    a fixed seeded sample of the envs (ascending `env_index`), the same for every array."""
+    import numpy as np
+
+    cols = {k: getattr(env, k) for k in ("pos_x", "pos_y", "rm_q", "flags", "t", "ep_ret", "reward", "shaping",
+                                         "env_done")}
+    cols = {k: v.cpu().numpy() for k, v in cols.items() if v is not None}
+    out = {k: v.astype(np.float32 if v.dtype in (np.float32, np.uint8) else np.float64) for k, v in cols.items()}
+    per_env = sum(v.nbytes for v in out.values()) // env.N
+    if per_env * env.N > max_bytes:
+        idx = np.sort(np.random.default_rng(0).choice(env.N, max_bytes // (per_env + 8), replace=False))
+        out = {k: np.ascontiguousarray(v[..., idx]) for k, v in out.items()}
+        out["env_index"] = idx.astype(np.float64)
+    out["report"] = np.asarray(report, np.float64)
+    return out
+
+
+def write_outputs(dirname, arrays, suffix=""):
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
 
 
 def pmc_entry(cfg_id, n_envs, variant=""):
@@ -856,8 +922,16 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: event windows and roofline, chain, dispatch "
+                         "stamps, rollout, the other configs, bandwidth regime, CPU baseline, parity, detail file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays the last reported window's last step left a caller as DIR/<name>.npy")
+    ap.add_argument("--act-buf-mb", type=int, default=ACT_BUF_BYTES >> 20,
+                    help="MiB of action rows kept in HBM per config; a longer window reads them cyclically")
     ap.add_argument("--config", type=int, default=None,
-                    help="time only this BASELINE config (2,3,4,5); default: config 2 headline + every other config")
+                    help="time only this BASELINE config (2,3,4,5); default: config 2 headline + with --full every "
+                         "other config")
     ap.add_argument("--n-envs", type=int, default=65536, help="envs per GPU")
     ap.add_argument("--graph", type=int, default=1, help="capture the timed steps in a HIP graph")
     ap.add_argument("--dispatch", choices=["queue", "graph"], default="queue",
@@ -967,8 +1041,9 @@ def run_rank(args):
 
     K, W = args.steps, args.warmup
 
-    def timed_config(cfg_id, random_starts=False, windows=None):
-        """The protocol of the module docstring for one BASELINE config; returns per-window samples."""
+    def timed_config(cfg_id, random_starts=False, windows=None, dump=None):
+        """The protocol of the module docstring for one BASELINE config; returns per-window samples.  `dump` (a
+        dict) receives step_outputs of the last reported window."""
         desc = T.baseline_scenario(cfg_id)
         if args.slip:  # characterisation: the env's own slip switch on (frozen_lake_stochastic / stochastic)
             desc = dict(desc, stochastic=True)
@@ -984,59 +1059,69 @@ def run_rank(args):
                        with_renv=False, with_env_done=True)
         stream = torch.cuda.current_stream()
         # inputs resident in HBM before timing: warmup + timed actions from the counter hash, one buffer
-        # refilled per window seed (the graph captures its address)
-        acts = env.fill_actions(WINDOW_SEEDS[0], 0, W + K)
+        # refilled per window seed (the graph captures its address); cyclic beyond ACT_BUF_BYTES of rows
+        T_buf = max(1, min(W + K, (args.act_buf_mb << 20) // (4 * tab.n_agents * N)))
+        acts = env.fill_actions(WINDOW_SEEDS[0], 0, T_buf)
         for s in range(W):
-            env.step(acts[s])
+            env.step(acts[s % T_buf])
         # the statistics report of a window: fused into the K-th step's launch (rmx_step_report) where the
         # handle's kernel allows it, else that step then the stats launch; the event windows time K plain steps
         report = torch.zeros(4, dtype=torch.float64, device=f"cuda:{local}")
 
-        def steps(reported):
-            for s in range(K - 1 if reported else K):
-                env.step(acts[W + s])
+        def steps(reported, g0=W, n=K):
+            for s in range(n - 1 if reported else n):
+                env.step(acts[(g0 + s) % T_buf])
             if reported:
-                env.step_report(acts[W + K - 1], out=report)
+                env.step_report(acts[(g0 + n - 1) % T_buf], out=report)
 
         # the reported windows: one rmx_step_seq (K dispatch packets on the engine's own AQL queue, blocking) where
         # the handle's step allows it, else a HIP graph replay; the event windows always replay a graph of K plain
-        # steps on the stream (HIP events time the same kernel there)
+        # steps on the stream (HIP events time the same kernel there).  A window longer than the action buffer is
+        # one such call per contiguous run of rows (act_segments), the report in the last
         use_queue = args.dispatch == "queue" and env.step_variant == "fast"
-        win_acts = acts[W:W + K]  # a view: refilled in place per window seed, same address
-        seq, queue_error = None, None
+        segs = act_segments(W, K, T_buf)  # [(W, K)] while the window fits the buffer
+        seg_keys = [(r, m, i == len(segs) - 1) for i, (r, m) in enumerate(segs)]
+        seqs, queue_error = {}, None
         if use_queue:
-            try:  # one untimed window: a queue that cannot start is reported (queue_error), the graph then runs
-                seq = env.seq_window(win_acts, out=report)  # checked once, bound
-                seq()
+            try:  # one untimed call: a queue that cannot start is reported (queue_error), the graph then runs
+                for r, m, last in seg_keys:  # views: refilled in place per window seed, same address
+                    seqs[(r, m, last)] = env.seq_window(acts[r:r + m], out=report if last else None)  # checked, bound
+                seqs[seg_keys[-1]]()
             except RuntimeError as e:
-                seq, use_queue, queue_error = None, False, str(e)[:300]
+                seqs, use_queue, queue_error = {}, False, str(e)[:300]
                 print(f"bench.py: the engine's queue failed, windows through a HIP graph: {e}", file=sys.stderr)
-        graph = graph_ev = None
-        if args.graph:
+        graphs, graph_ev = {}, None
+        if args.graph and (args.full or not use_queue):
             s0 = torch.cuda.Stream()
             s0.wait_stream(stream)
-            graph, graph_ev = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with torch.cuda.stream(s0):
                 if not use_queue:
-                    with torch.cuda.graph(graph, stream=s0):
-                        steps(True)
-                with torch.cuda.graph(graph_ev, stream=s0):
-                    steps(False)
+                    for r, m, last in set(seg_keys):
+                        graphs[(r, m, last)] = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(graphs[(r, m, last)], stream=s0):
+                            steps(last, r, m)
+                if args.full:
+                    graph_ev = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph_ev, stream=s0):
+                        steps(False)
             stream.wait_stream(s0)
-            if use_queue:
-                graph = None
-            else:
-                graph.replay()  # untimed: the first replay of a graph pays its upload (+1.5 us per step at K=20)
-            graph_ev.replay()
+            for g in graphs.values():
+                g.replay()  # untimed: the first replay of a graph pays its upload (+1.5 us per step at K=20)
+            if graph_ev is not None:
+                graph_ev.replay()
 
+        if seqs:
+            runs = [seqs[k] for k in seg_keys]
+        elif graphs:
+            runs = [graphs[k].replay for k in seg_keys]
+        else:
+            runs = [lambda r=r, m=m, last=last: steps(last, r, m) for r, m, last in seg_keys]
 
-        def reported_steps():
-            if seq is not None:
-                seq()
-            elif graph is not None:
-                graph.replay()
-            else:
-                steps(True)
+        def all_runs():
+            for run in runs:
+                run()
+
+        reported_steps = runs[0] if len(runs) == 1 else all_runs  # the K steps of a reported window
 
         torch.cuda.synchronize()
         # no collector pause inside a ~70-us window (as timeit does); collected before the spin-up, so the GPU is
@@ -1045,21 +1130,31 @@ def run_rank(args):
         gc.disable()
         # untimed spin-up: ~--spin-ms of back-to-back steps so the timed windows do not start on an idle-clocked
         # GPU (after an idle gap the first 20-step windows ran at 4.7-5.5 us per step instead of 3.6)
-        t_spin = time.perf_counter() + args.spin_ms / 1e3
+        t_spin0 = time.perf_counter()
+        t_spin, spun = t_spin0 + args.spin_ms / 1e3, 0
         while time.perf_counter() < t_spin:
-            reported_steps()
-            torch.cuda.synchronize()
+            for (_, m), run in zip(segs, runs):
+                run()
+                torch.cuda.synchronize()
+                spun += m
+                if time.perf_counter() >= t_spin:
+                    break
+        # the spin-up's time per step says how long a window (warmup + K steps) takes: the windows that fit the budget
+        window_s = (time.perf_counter() - t_spin0) / spun * (W + K) if spun else 0.0
         RD.allreduce_stats(env.stats_tensor(), coll_dev)  # untimed: the collective's first call sets up its channels
         torch.cuda.synchronize()
+        if world > 1:  # every rank runs the same windows
+            window_s = RD.max_over_ranks([window_s], coll_dev)[0]
+        seeds, discard_first = window_plan(n_windows, window_s)
         q0 = env.queue_counters()
 
         def prep(seed):
             """A window's inputs and state: this seed's actions in the one buffer, a reset, the W warmup steps."""
-            env.fill_actions(seed, 0, W + K, out=acts)
+            env.fill_actions(seed, 0, T_buf, out=acts)
             env.reset()
             env.clear_stats()
             for s in range(W):
-                env.step(acts[s])
+                env.step(acts[s % T_buf])
 
         def window(seed, events):
             """One timed window.  The wall-clock windows carry no HIP events: recording them around the graph
@@ -1094,17 +1189,20 @@ def run_rank(args):
                     "ev_steps_s": ev0.elapsed_time(ev1) / 1e3 if events else None, "stats": st.cpu().numpy()}
 
         try:
-            window(WINDOW_SEEDS[0], False)  # discarded: the first window after the spin-up often ran slow
-            samples = [window(WINDOW_SEEDS[w % len(WINDOW_SEEDS)], False) for w in range(n_windows)]
-            ev_samples = [window(WINDOW_SEEDS[w % len(WINDOW_SEEDS)], True) for w in range(n_windows)]
+            if discard_first:
+                window(WINDOW_SEEDS[0], False)  # discarded: the first window after the spin-up often ran slow
+            samples = [window(seed, False) for seed in seeds]
+            if dump is not None:  # what the last reported window's last step left, before anything else steps the envs
+                dump.update(step_outputs(env, samples[-1]["stats"]))
+            ev_samples = [window(seed, True) for seed in seeds] if args.full else []
         finally:
             gc.enable()
         q1 = env.queue_counters()
         q_state = env.queue_info()["state"]
-        chain_s = chain_launch_s(env, acts[W], stream) if args.graph and args.chain > 0 else None
-        cp = cp_dispatch_times(env, seq, K, prep) if use_queue else None
+        chain_s = chain_launch_s(env, acts[W % T_buf], stream) if args.full and args.graph and args.chain > 0 else None
+        cp = cp_dispatch_times(env, runs[0], K, prep) if args.full and use_queue and len(runs) == 1 else None
         env.check_errors()
-        del graph, graph_ev
+        del graphs, graph_ev
         walls = [x["wall_s"] for x in samples]
         med = sorted(range(len(walls)), key=lambda i: walls[i])[len(walls) // 2]
         m = samples[med]
@@ -1113,8 +1211,7 @@ def run_rank(args):
         # random starts (4 B per two agents per env; the fixed-start cache)
         B = (algorithmic_bytes_per_instance_step(A, tab.shape is not None) + (48.0 / A if args.slip else 0.0)
              + (4.0 * ((A + 1) // 2) / A if random_starts else 0.0))
-        launch_s = statistics.median(x["ev_steps_s"] for x in ev_samples) / K
-        achieved = N * A * B / launch_s / 1e9
+        launch_s = statistics.median(x["ev_steps_s"] for x in ev_samples) / K if ev_samples else None
         st = m["stats"]
         out = {
             "config": cfg_id, "workload": WORKLOADS[cfg_id] + (", slip dynamics" if args.slip else "")
@@ -1122,7 +1219,7 @@ def run_rank(args):
             "n_envs_per_gpu": N, "n_envs_total": world * N,
             "n_agents": A, "rm_states": tab.n_rm_states, "kernel": KERNEL_NAMES[env.step_variant],
             "value": world * N * A * K / m["wall_s"], "unit": "(env x agent)-steps/s",
-            "ms_per_step": m["wall_s"] * 1e3 / K, "us_per_step_event": launch_s * 1e6,
+            "ms_per_step": m["wall_s"] * 1e3 / K, "us_per_step_event": launch_s * 1e6 if launch_s else None,
             # the window's statistics all-reduce (N > 1: one RCCL collective of 32 B), timed on its own, and the
             # throughput if every K-step window also paid it
             "allreduce_us": statistics.median(x["allreduce_s"] for x in samples) * 1e6,
@@ -1136,19 +1233,23 @@ def run_rank(args):
                         for x in samples],
             "event_windows": [{"seed": x["seed"], "us_per_step_event": x["ev_steps_s"] * 1e6 / K,
                                "us_per_step_wall": x["wall_s"] * 1e6 / K} for x in ev_samples],
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(cfg_id, N, variant),
-                         "frac_counter": frac_counter(pmc_traffic(cfg_id, N, variant), launch_s),
-                         "traffic_source": pmc_source(cfg_id, N, variant, BUILD.get("src"), BUILD.get("kern")),
-                         "bytes_per_launch": N * A * B, "bytes_per_instance_step": B,
-                         "avg_launch_us": launch_s * 1e6,
-                         "chain_launch_us": chain_s * 1e6 if chain_s else None,
-                         "floor": None if variant else copy_floor(N, launch_s * 1e6, cfg_id,
-                                                                    chain_s * 1e6 if chain_s else None),
-                         "kernel": KERNEL_NAMES[env.step_variant]},
+            "roofline": None,  # from the event windows (--full), below
             "episode_stats": {"episodes": float(st[1]), "mean_return_per_agent_episode": float(st[0] / max(st[1] * A, 1)),
                               "successes": float(st[2]), "mean_length": float(st[3] / max(st[1], 1))},
         }
+        if launch_s is None:
+            return tab, env, out
+        achieved = N * A * B / launch_s / 1e9
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(cfg_id, N, variant),
+                           "frac_counter": frac_counter(pmc_traffic(cfg_id, N, variant), launch_s),
+                           "traffic_source": pmc_source(cfg_id, N, variant, BUILD.get("src"), BUILD.get("kern")),
+                           "bytes_per_launch": N * A * B, "bytes_per_instance_step": B,
+                           "avg_launch_us": launch_s * 1e6,
+                           "chain_launch_us": chain_s * 1e6 if chain_s else None,
+                           "floor": None if variant else copy_floor(N, launch_s * 1e6, cfg_id,
+                                                                      chain_s * 1e6 if chain_s else None),
+                           "kernel": KERNEL_NAMES[env.step_variant]}
         if not variant:  # the committed counter pass's per-dispatch time of this kernel (profiles/profile_times.json)
             out["roofline"].update(profile_time(cfg_id, N, N * A * B, BUILD.get("kern")) or {})
         if cp:  # the profile time of this run: the command processor's stamps of the same windows' dispatches
@@ -1164,12 +1265,16 @@ def run_rank(args):
                             strict=world > 1 and backend == "nccl", device=coll_dev)
 
     head_cfg = args.config or 2
-    tab, env, head = timed_config(head_cfg)
+    outputs = {} if args.dump_outputs else None
+    tab, env, head = timed_config(head_cfg, dump=outputs)
     N, A = head["n_envs_per_gpu"], head["n_agents"]
     stream = torch.cuda.current_stream()
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs, "" if world == 1 else f"_rank{rank}")
 
+    # from here to the result line: --full only
     rollout = None
-    if not args.no_rollout:
+    if args.full and not args.no_rollout:
         env.reset()
         env.clear_stats()
         env.rollout(0, 0, 10)  # warm
@@ -1190,7 +1295,7 @@ def run_rank(args):
     env.close()
 
     others = {}
-    if args.config is None:  # every other BASELINE GPU config by the same protocol, on every rank
+    if args.full and args.config is None:  # every other BASELINE GPU config by the same protocol, on every rank
         for c in (3, 4, 5):
             t_c, e_c, o_c = timed_config(c)
             e_c.close()
@@ -1200,7 +1305,7 @@ def run_rank(args):
         if rank == 0 and world == 1 and args.dict_seconds > 0:  # BASELINE config 1: the dict API at N = 1
             others["1"] = dict_api_leg(local, args.dict_seconds)
     rs_legs = {}
-    if args.config is None and not args.random_starts and args.rs_configs:
+    if args.full and args.config is None and not args.random_starts and args.rs_configs:
         # the FrozenLake configs with random_start_positions on (the reference runner's schedule): characterisation
         for c in (int(x) for x in args.rs_configs.split(",")):
             t_c, e_c, o_c = timed_config(c, random_starts=True)
@@ -1219,11 +1324,11 @@ def run_rank(args):
     attach_rank_dispatch(dist, world, coll, mine)
 
     large = None
-    if args.large_envs > 0 and world == 1:  # single-GPU characterisation only
+    if args.full and args.large_envs > 0 and world == 1:  # single-GPU characterisation only
         large = bandwidth_regime(tab, args.large_envs, 20, local, head_cfg)
 
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         info = host_cpu()
         threads = args.cpu_threads or baseline_threads(info)
         cpu = cpu_baseline(tab, 65536, args.cpu_seconds, threads, info)
@@ -1234,7 +1339,8 @@ def run_rank(args):
     if rank == 0:
         detail = assemble_detail(args, world, head_cfg, head, others, rs_legs, coll, cpu, parity, rollout, large,
                                  pinned)
-        print(json.dumps(compact_line(detail, write_detail(detail, args.detail, world))), flush=True)
+        path = write_detail(detail, args.detail, world) if args.full or args.detail else None
+        print(json.dumps(compact_line(detail, path)), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
@@ -1273,8 +1379,8 @@ def dry_run(args, rank, world):
     collective_block (all_gather), barrier, aligned_start (MAX), the statistics all-reduce (rmx.dist.allreduce_stats)
     and the window's max over ranks (rmx.dist.max_over_ranks), every tensor on the collective device as the RCCL run
     has it on its GPU (here gloo's: the host, so no copy is made, exactly as under RCCL); then the per-rank dispatch
-    rows, the detail file and the compact line of a full run (every config, random-start legs, collective), marked
-    dry_run with `value` null."""
+    rows, the detail file and the compact line of a --full run (every config, random-start legs, collective) or,
+    without --full, of a plain one, marked dry_run with `value` null."""
     import torch
     import torch.distributed as dist
 
@@ -1309,7 +1415,7 @@ def dry_run(args, rank, world):
     q0 = {"windows": 0, "uploads": 0, "packets": 0, "stream_windows": 0, "recordings": 0}
     attach_rank_dispatch(dist if world > 1 else None, world, coll, {
         k: {"dispatch": "dry-run", "queue_counters": dict(q0), "queue_state": "unused"}
-        for k in ("2", "3", "4", "5", "rs2", "rs4")})
+        for k in (("2", "3", "4", "5", "rs2", "rs4") if args.full else ("2",))})
     shards = [torch.zeros(2, dtype=torch.int64, device=dev) for _ in range(world)]
     if world > 1:
         dist.all_gather(shards, torch.tensor([offset, n], dtype=torch.int64, device=dev))
@@ -1326,8 +1432,12 @@ def dry_run(args, rank, world):
               for c, A in (("2", 2), ("4", 4))}
         cpu = {"value": 0.0, "unit": "(env x agent)-steps/s", "cores": 1, "kind": "port",
                "host": host_cpu(), "sample": "dry-run", "single_thread": {"value": 0.0}}
-        detail = assemble_detail(args, world, 2, head, others, rs, coll, cpu, head["parity"], None, None, None)
-        line = compact_line(detail, write_detail(detail, args.detail, world))
+        parity = head["parity"]
+        if not args.full:  # a plain run's line: the headline config's windows alone
+            others, rs, cpu, parity = {}, {}, None, None
+            head.update(roofline=None, us_per_step_event=None, event_windows=[])
+        detail = assemble_detail(args, world, 2, head, others, rs, coll, cpu, parity, None, None, None)
+        line = compact_line(detail, write_detail(detail, args.detail, world) if args.full or args.detail else None)
         line.update(value=None, dry_run=True, shards=[s.tolist() for s in shards], stats_allreduced=st.tolist(),
                     aligned_start_late_s=skew)
         print(json.dumps(line), flush=True)

@@ -26,7 +26,7 @@ kind=$1 OUT=$2
 shift 2 || { echo "usage: bash scripts/gpu.sh KIND OUT [TAG] [args]"; exit 2; }
 mkdir -p "$OUT"
 fail() { echo "gpu.sh $kind $TAG: exit $1"; tail -${2:-30} "$3"; exit "$1"; }
-PROF_BENCH="--graph 0 --dispatch graph --spin-ms 50 --no-cpu-baseline --no-rollout --large-envs 0 --dict-seconds 0 --rs-configs="
+PROF_BENCH="--full --graph 0 --dispatch graph --spin-ms 50 --no-cpu-baseline --no-rollout --large-envs 0 --dict-seconds 0 --rs-configs="
 case $kind in
   smoke)
     TAG=smoke
@@ -39,7 +39,7 @@ case $kind in
     tail -2 "$OUT/tests_$TAG.txt" ;;
   bench)
     TAG=$1; shift
-    timeout -k 10 600 python -u bench.py "$@" > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err" || fail $? 30 "$OUT/bench_$TAG.err"
+    timeout -k 10 600 python -u bench.py --full "$@" > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err" || fail $? 30 "$OUT/bench_$TAG.err"
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('bench', sys.argv[2], round(d['value']/1e9, 2), 'G/s', \
 round(d['us_per_step_event'], 3), 'us/step (events)')" "$OUT/bench_$TAG.json" "$TAG" ;;
   variants)

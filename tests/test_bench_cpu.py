@@ -26,7 +26,7 @@ LINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_ste
 @pytest.mark.parametrize("n", [1, 2, 3, 8])
 def test_gpus_flag_launches_that_many_ranks(n, tmp_path):
     detail_path = str(tmp_path / "detail.json")
-    r = _run(["--gpus", str(n), "--dry-run", "--n-envs", "1000", "--detail", detail_path])
+    r = _run(["--gpus", str(n), "--dry-run", "--full", "--n-envs", "1000", "--detail", detail_path])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout  # rank 0's JSON line and nothing else
@@ -66,6 +66,83 @@ def test_gpus_flag_launches_that_many_ranks(n, tmp_path):
         x = r["dispatch"]["2"]
         assert x["dispatch"] == "dry-run" and x["queue_state"] == "unused"
         assert set(x["queue_counters"]) == {"windows", "uploads", "packets", "stream_windows", "recordings"}
+
+
+def test_plain_run_line_keeps_the_contract_keys_and_measures_nothing_else(tmp_path):
+    """Without --full the line still has every key, the headline's `ms_per_step` among them, and null or empty for
+    what only --full measures; no detail file is written unless --detail names one."""
+    r = _run(["--gpus", "1", "--dry-run", "--n-envs", "1000", "--steps", "20", "--warmup", "5"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert all(k in out for k in LINE_KEYS), [k for k in LINE_KEYS if k not in out]
+    assert out["steps"] == 20 and out["warmup"] == 5 and out["ms_per_step"] > 0 and out["higher_is_better"] is True
+    assert out["dtype"] == "int32" and out["unit"] == "(env x agent)-steps/s"
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["parity"] is None
+    assert out["configs"] == {} and out["roofline_large"] is None and out["detail"] is None
+
+
+def test_action_segments_and_window_plan():
+    """bench.act_segments: a window is one run of rows while it fits the action buffer, else the cyclic buffer's
+    contiguous runs in step order; bench.window_plan: the nominal seeds while the windows fit the budget, else the
+    sequence's tail (the last seed fixed), the discarded window only beside two more."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.act_segments(100, 1000, 1100) == [(100, 1000)]
+    assert bench.act_segments(5, 20, 8) == [(5, 3), (0, 8), (0, 8), (0, 1)]
+    assert bench.act_segments(8, 16, 8) == [(0, 8), (0, 8)]
+    for g0, n, rows in ((0, 1, 1), (7, 50, 13), (100, 4096, 1024)):
+        segs = bench.act_segments(g0, n, rows)
+        assert sum(m for _, m in segs) == n and all(0 <= r and m >= 1 and r + m <= rows for r, m in segs)
+        assert [(r + i) for r, m in segs for i in range(m)] == [(g0 + s) % rows for s in range(n)]
+    seeds = list(bench.WINDOW_SEEDS)
+    assert bench.window_plan(5, 1e-4) == (seeds, True) and bench.window_plan(5, 0.0) == (seeds, True)
+    assert bench.window_plan(5, 2.0, 10.0) == (seeds[-4:], True)
+    assert bench.window_plan(5, 4.0, 10.0) == (seeds[-1:], True)
+    assert bench.window_plan(5, 6.0, 10.0) == (seeds[-1:], False)
+    assert bench.window_plan(5, 60.0, 10.0) == (seeds[-1:], False)
+    assert bench.window_plan(7, 1e-4)[0] == [bench.WINDOW_SEEDS[w % 5] for w in range(7)]
+
+
+def test_step_outputs_arrays_and_sample(tmp_path):
+    """bench.step_outputs / write_outputs: every column and the report as float32 / float64 .npy, integers exact;
+    past the byte limit the same fixed, seeded, ascending sample of the envs for every array."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Env:
+        N = 1000
+        pos_x = torch.arange(2000, dtype=torch.int32).reshape(2, 1000)
+        pos_y = pos_x + 1
+        rm_q = pos_x % 4
+        flags = torch.full((2, 1000), 0x7FFFFFFF, dtype=torch.int32)
+        t = torch.arange(1000, dtype=torch.int32)
+        ep_ret = torch.rand(2, 1000)
+        reward = torch.rand(2, 1000)
+        shaping = None
+        env_done = (t % 3 == 0).to(torch.uint8)
+
+    rep = np.array([1.5, 2.0, 1.0, 40.0])
+    out = bench.step_outputs(Env, rep)
+    assert set(out) == {"pos_x", "pos_y", "rm_q", "flags", "t", "ep_ret", "reward", "env_done", "report"}
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values())
+    assert out["flags"].dtype == np.float64 and (out["flags"] == float(0x7FFFFFFF)).all()
+    np.testing.assert_array_equal(out["pos_x"], Env.pos_x.numpy())
+    np.testing.assert_array_equal(out["reward"], Env.reward.numpy())
+    np.testing.assert_array_equal(out["report"], rep)
+    small = bench.step_outputs(Env, rep, max_bytes=10_000)
+    idx = small["env_index"].astype(np.int64)
+    assert 0 < len(idx) < 1000 and (np.diff(idx) > 0).all()
+    assert sum(v.nbytes for v in small.values()) <= 10_000 + rep.nbytes
+    np.testing.assert_array_equal(small["pos_y"], Env.pos_y.numpy()[:, idx])
+    np.testing.assert_array_equal(small["t"], Env.t.numpy()[idx])
+    np.testing.assert_array_equal(bench.step_outputs(Env, rep, max_bytes=10_000)["env_index"], small["env_index"])
+    bench.write_outputs(str(tmp_path / "d"), small)
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(k + ".npy" for k in small)
+    np.testing.assert_array_equal(np.load(tmp_path / "d" / "rm_q.npy"), small["rm_q"])
 
 
 def test_compact_line_of_a_full_detail_stays_small():
