@@ -25,6 +25,9 @@
  * wherever it says "device" (buffers, actions, masks, statistics, traces), ignores the stream and completes before it
  * returns.  It is the reference's own CPU case (BASELINE config 1: one env behind the per-call dict API) without a GPU
  * or a PCIe round trip per call.  rmx_step_variant reports RMX_VARIANT_HOST; rmx_step_seq, RMX_SEQ_HOST.
+ * A host handle keeps the device's table limit: tables whose generic-kernel blob would exceed 64 KiB of LDS are refused
+ * by rmx_create on either path (RMX_E_INVALID, "tables exceed 64 KiB ..."), so a config that a host handle steps is one
+ * a device handle steps too.
  */
 #ifndef RMX_H
 #define RMX_H
@@ -36,7 +39,7 @@
 extern "C" {
 #endif
 
-#define RMX_ABI_VERSION 11
+#define RMX_ABI_VERSION 12
 
 /* ---- limits (tables are staged whole into LDS per workgroup) ---------------------------------- */
 #define RMX_MAX_AGENTS 8
@@ -310,6 +313,32 @@ int rmx_code_object_check(const void* co, size_t bytes, int64_t* n_step_kernels,
 #define RMX_VARIANT_FAST_LANE_PER_AGENT 3
 #define RMX_VARIANT_HOST 4 /* a host handle (cfg.device == RMX_DEVICE_HOST): the CPU path */
 int rmx_step_variant(const rmx_handle* h);
+
+/* The kernel configuration rmx_create chose for this handle, after every fallback (no device work; no reference
+ * counterpart): out[0..n) of RMX_STEP_INFO_N values.
+ *   [0]  the step variant, as rmx_step_variant returns it
+ *   [1]  the table mode the step kernel reads (RMX_TABLES_*): NONE for the generic kernels and host handles; GLOBAL
+ *        also where QRM outputs are bound to a fast handle (the move word carries the event they need)
+ *   [2]  bytes per merged record the step kernel reads: 16, 4 (RMX_TABLES_MERGED4), or 0 (no merged table read)
+ *   [3]  agent sections stored in the merged table after identical ones are shared (0: no merged table)
+ *   [4]  bytes of the 16-B merged records, [5] bytes of the 4-B records that follow them (0: none built)
+ *   [6]  bytes of the fast path's blob (move words, RM entries; 0: the config is not eligible or RMX_FAST=0)
+ *   [7]  bytes of the generic kernels' table blob (<= 64 KiB)
+ *   [8]  the store mode of the step kernel in [0]: the fast kernel's (2 rm_q / ep_ret stores skipped when unchanged,
+ *        3 the same with non-temporal stores) or the generic kernel's (0 every word stored, 1 unchanged words skipped)
+ *   [9]  episode statistics: 1 per-wave slab, 0 per-env slots (fast kernel below 1M envs)
+ *   [10] workgroup size of the step kernel
+ *   [11] 1 if QRM outputs are bound and the fast kernel serves them
+ *   [12] 1 if slip / random starts use the fixed-seed reset cache (seed_episode_stride == 0 on a fast handle)
+ *   [13] the fused rollout's layout: 0 thread-per-env, 1 lane-per-agent
+ * [0], [1], [2], [8], [10] and [11] depend on the bound buffers (QRM columns): ask after rmx_bind.
+ * A host handle reports RMX_VARIANT_HOST and zeros. */
+#define RMX_STEP_INFO_N 14
+#define RMX_TABLES_NONE 0
+#define RMX_TABLES_GLOBAL 1
+#define RMX_TABLES_MERGED 2
+#define RMX_TABLES_MERGED4 3
+int rmx_step_info(const rmx_handle* h, int64_t* out, int32_t n);
 
 /* Synchronise and report kernel-side errors (e.g. RMX_E_ACTION), then clear them. */
 int rmx_check_errors(rmx_handle* h);

@@ -105,6 +105,7 @@ struct rmx_handle {
   void* d_fast = nullptr;
   void* d_merged = nullptr;  // kTblMerged table (RMX_FAST_TABLES=merged or the default where measured faster)
   size_t merged_bytes = 0;
+  int merged_sections = 0;  // agent sections stored in d_merged (identical ones shared)
   // fast-path episode statistics: es_ret [N] f64 | es_cnt [N] u64 | es_succ [N] u32
   unsigned char* d_es = nullptr;
   size_t es_bytes = 0;
@@ -852,6 +853,11 @@ int rmx_create(const rmx_config* cfg, rmx_handle** out) {
         h->fast_tables = rmx::kTblMerged;  // shaping or > 4 distinct rewards: the 16-B records
       }
     }
+    if (h->fast && h->fast_tables != rmx::kTblGlobal) {
+      const size_t sec_words = (size_t)cfg->n_rm_states * cfg->width * cfg->height * 5 * 4;
+      const size_t words16 = h->merged4_bytes ? h->merged4_off / 4 : merged_tab.size();
+      h->merged_sections = (int)(words16 / sec_words);
+    }
   }
   // slip / random starts under seed_episode_stride == 0 (the reference FrozenLake runner's reset(args.seed) every
   // episode, frozen_lake_main.py:337): every episode of an env starts from the same generator and shuffle, so the
@@ -1469,6 +1475,33 @@ int rmx_step_variant(const rmx_handle* h) {
   if (h->host) return RMX_VARIANT_HOST;
   if (fast_applies(h)) return RMX_VARIANT_FAST;
   return h->step_layout == rmx::kLayoutLanePerAgent ? RMX_VARIANT_LANE_PER_AGENT : RMX_VARIANT_GENERIC;
+}
+
+int rmx_step_info(const rmx_handle* h, int64_t* out, int32_t n) {
+  if (!h || !out || n < 0) return fail(RMX_E_INVALID, "bad rmx_step_info arguments");
+  int64_t v[RMX_STEP_INFO_N] = {};
+  v[0] = rmx_step_variant(h);
+  if (!h->host) {
+    const bool fast = fast_applies(h);
+    const bool qrm = fast && h->buf.qrm_s && h->cfg.n_qrm_max > 0;
+    const int tm = !fast ? 0 : qrm ? rmx::kTblGlobal : h->fast_tables;  // step_fp: QRM outputs read the global blob
+    v[1] = tm == rmx::kTblGlobal ? RMX_TABLES_GLOBAL : tm == rmx::kTblMerged ? RMX_TABLES_MERGED
+         : tm == rmx::kTblMerged4 ? RMX_TABLES_MERGED4 : RMX_TABLES_NONE;
+    v[2] = tm == rmx::kTblMerged ? 16 : tm == rmx::kTblMerged4 ? 4 : 0;
+    v[3] = h->merged_sections;
+    v[4] = h->merged_sections ? (int64_t)h->merged_bytes : 0;  // (a table that outgrew kMergedMaxBytes is not used)
+    v[5] = (int64_t)h->merged4_bytes;
+    v[6] = h->fast ? (int64_t)h->fast_n16 * 16 : 0;
+    v[7] = (int64_t)h->tables_bytes;
+    v[8] = fast ? h->fast_skip : h->generic_skip;
+    v[9] = fast ? h->fast_wave_stats : 1;
+    v[10] = fast ? h->fast_block : h->block;
+    v[11] = qrm ? 1 : 0;
+    v[12] = h->seed_fixed ? 1 : 0;
+    v[13] = h->rollout_layout;
+  }
+  for (int32_t i = 0; i < n && i < RMX_STEP_INFO_N; ++i) out[i] = v[i];
+  return RMX_OK;
 }
 
 int rmx_state_bytes(const rmx_handle* h, size_t* bytes) {

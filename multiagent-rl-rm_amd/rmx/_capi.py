@@ -27,17 +27,24 @@ EXPORTS = (
     "rmx_stats_clear", "rmx_check_errors", "rmx_mdp_states", "rmx_mdp", "rmx_step_variant", "rmx_state_bytes",
     "rmx_get_state", "rmx_set_state", "rmx_step_report", "rmx_step_report_fused", "rmx_reset_sync", "rmx_step_sync",
     "rmx_step_sync_begin", "rmx_sync_wait", "rmx_sync_end", "rmx_step_seq", "rmx_queue_counters", "rmx_queue_info",
-    "rmx_code_object_check", "rmx_device_count", "rmx_queue_timing", "rmx_queue_times",
+    "rmx_code_object_check", "rmx_device_count", "rmx_queue_timing", "rmx_queue_times", "rmx_step_info",
 )
 SYNC_MAX_ENVS = 256  # RMX_SYNC_MAX_ENVS
 QUEUE_INFO_N = 7  # RMX_QUEUE_INFO_N
 QUEUE_STATES = ("unused", "ready", "unavailable", "retired")  # RMX_QUEUE_*
 SEQ_DISPATCH = ("none", "queue", "stream:kernel", "stream:disabled", "stream:queue", "host")  # RMX_SEQ_*
 VARIANT_GENERIC, VARIANT_LANE_PER_AGENT, VARIANT_FAST, VARIANT_FAST_LANE_PER_AGENT, VARIANT_HOST = 0, 1, 2, 3, 4
+STEP_INFO_N = 14  # RMX_STEP_INFO_N
+STEP_INFO_FIELDS = ("variant", "tables", "record_bytes", "merged_sections", "merged_bytes", "merged4_bytes",
+                    "fast_blob_bytes", "generic_blob_bytes", "store_mode", "wave_stats", "block", "qrm_fast",
+                    "seed_fixed", "rollout_layout")
+VARIANT_NAMES = ("generic", "lane_per_agent", "fast", "fast_lpe", "host")  # RMX_VARIANT_*
+TABLE_MODES = ("none", "global", "merged", "merged4")  # RMX_TABLES_*
+LAYOUTS = ("thread_per_env", "lane_per_agent")
 DEVICE_HOST = -1  # RMX_DEVICE_HOST: rmx_config.device of a host handle (the CPU path, csrc/rmx_hoststep.cpp)
 
 
-ABI_VERSION = 11  # include/rmx.h RMX_ABI_VERSION
+ABI_VERSION = 12  # include/rmx.h RMX_ABI_VERSION
 
 # The sources whose SHA-256 (concatenated in this order) librmx.so reports through rmx_build_info(): the same
 # list as RMX_HASHED in csrc/Makefile (tests/test_capi.py checks that they agree).
@@ -201,6 +208,7 @@ def load_library(path: str = None, check_source: bool = True):
         "rmx_queue_times": (C.c_int, [vp, vp, C.c_int64, C.POINTER(C.c_int64)]),
         "rmx_queue_counters": (C.c_int, [vp, vp]),
         "rmx_queue_info": (C.c_int, [vp, vp, i32]),
+        "rmx_step_info": (C.c_int, [vp, vp, i32]),
         "rmx_code_object_check": (C.c_int, [vp, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p,
                                             C.c_size_t]),
         "rmx_mdp_states": (C.c_int, [vp, i32, C.POINTER(C.c_int64)]),

@@ -282,6 +282,20 @@ class VecRMEnv:
         return {_capi.VARIANT_FAST: "fast", _capi.VARIANT_FAST_LANE_PER_AGENT: "fast_lpe",
                 _capi.VARIANT_GENERIC: "generic", _capi.VARIANT_LANE_PER_AGENT: "lane_per_agent"}[v]
 
+    @property
+    def step_info(self) -> dict:
+        """rmx_step_info: the kernel configuration chosen at construction, after every fallback.  "variant", "tables"
+        ("none", "global", "merged", "merged4") and "rollout_layout" as names, the rest as ints (_capi.STEP_INFO_FIELDS:
+        record_bytes 16 / 4 / 0, merged_sections, the table sizes in bytes, store_mode, wave_stats, block, qrm_fast,
+        seed_fixed)."""
+        v = (C.c_int64 * _capi.STEP_INFO_N)()
+        _capi.check(self.lib.rmx_step_info(self._h, v, _capi.STEP_INFO_N), "rmx_step_info")
+        d = dict(zip(_capi.STEP_INFO_FIELDS, (int(x) for x in v)))
+        d["variant"] = _capi.VARIANT_NAMES[d["variant"]]
+        d["tables"] = _capi.TABLE_MODES[d["tables"]]
+        d["rollout_layout"] = _capi.LAYOUTS[d["rollout_layout"]]
+        return d
+
     def check_errors(self):
         _capi.check(self.lib.rmx_check_errors(self._h), "rmx_check_errors")
 
@@ -560,6 +574,7 @@ class HostRMEnv:
                 dst[...] = np.asarray(v).view(dst.dtype) if np.asarray(v).dtype.itemsize == dst.dtype.itemsize \
                     else np.asarray(v).astype(dst.dtype)
 
+    step_info = VecRMEnv.step_info  # (a host handle: variant "host", zeros)
     queue_info = VecRMEnv.queue_info  # (a host handle has no device queue: "unused"; step_seq reports "host")
     queue_timing = VecRMEnv.queue_timing  # (no-op on a host handle; queue_times is then empty)
     queue_times = VecRMEnv.queue_times

@@ -184,6 +184,43 @@ CONFIGS["fl2_randstart_slip"] = dict(CONFIGS["fl2_quirks"], stochastic=True, ran
 CONFIGS["fl4_randstart_open"] = dict(CONFIGS["fl2_open"], random_start_positions=True, seed_schedule=[1, 1, 1],
                                      agents=CONFIGS["fl2_open"]["agents"] + CONFIGS["fl2_open"]["agents"])
 
+# ---- field-width and table-mode limits (tests/test_limits_gpu.py): RM states and palette bytes past 127, 8 agents,
+# two reward palettes, 4 versus 5 distinct rewards, 16 versus 17 QRM states.  FrozenLake on custom layouts, the one
+# map form this recorder accepts off the named maps.  "record_qrm": False records without the QRM columns (their
+# [steps, A, Q-1, envs] arrays would run to hundreds of MB at 200 states) and with a learner that does not ask the
+# wrapper for qrm_experience.
+def _chain(n, rewards, fmt="s{:03d}"):
+    """s_k --A|B alternating--> s_{k+1}, k < n, rewards cycling; zero-padded names so that index == k."""
+    return [[fmt.format(k), "AB"[k % 2], fmt.format(k + 1), rewards[k % len(rewards)]] for k in range(n)]
+
+
+# (two cells: on a 4 x 3 lake the hashed walk advances the chain by ~0.09 states per step and never gets past state 90
+# in an episode; here every left / right step that moves advances it, ~0.25 per step)
+PAIR_LAKE = """
+A B
+"""
+CORNER_LAKE = """
+A B 🟩 🟩
+🟩 🟩 🟩 🟩
+🟩 🟩 🟩 🟩
+"""
+FL_CHAIN200 = _chain(200, [-128, 127, -3])
+CONFIGS["fl8_chain200"] = {"kind": "frozen_lake", "layout": PAIR_LAKE, "penalty": 0.0, "record_qrm": False,
+                           "agents": [{"start": [k % 2, 0], "rm": FL_CHAIN200} for k in range(8)]}
+CONFIGS["fl1_chain200"] = {"kind": "frozen_lake", "layout": PAIR_LAKE, "penalty": 0.0, "record_qrm": False,
+                           "agents": [{"start": [1, 0], "rm": FL_CHAIN200}]}
+FL_NEG3 = _chain(8, [-128, 127, -3], "s{}")
+FL_NEG2 = [["s0", "B", "s1", -128], ["s1", "A", "s2", 127], ["s2", "B", "s3", -128]]
+FL_PAL5 = _chain(8, [1, 2, 3, 4], "s{}")
+CONFIGS["fl2_negpal"] = {"kind": "frozen_lake", "layout": OPEN_LAKE, "penalty": 0.0,
+                         "agents": [{"start": [2, 2], "rm": FL_NEG3}, {"start": [3, 1], "rm": FL_NEG2}]}
+CONFIGS["fl2_pal5"] = {"kind": "frozen_lake", "layout": OPEN_LAKE, "penalty": 0.0,
+                       "agents": [{"start": [2, 2], "rm": FL_PAL5}, {"start": [3, 1], "rm": FL_NEG2}]}
+CONFIGS["fl1_qrm16"] = {"kind": "frozen_lake", "layout": CORNER_LAKE, "penalty": 0.0,
+                        "agents": [{"start": [2, 1], "rm": _chain(16, [1, -2, 3], "s{:02d}")}]}
+CONFIGS["fl1_qrm17"] = {"kind": "frozen_lake", "layout": CORNER_LAKE, "penalty": 0.0,
+                        "agents": [{"start": [2, 1], "rm": _chain(17, [1, -2, 3], "s{:02d}")}]}
+
 TRAJ = {  # cfg -> (n_envs, n_steps, seed)
     "fl2": (32, 1100, 0), "fl4": (16, 1100, 1), "fl2_quirks": (32, 1100, 2), "fl2_initfinal": (8, 300, 4),
     "fl2_finalnt": (16, 1100, 5), "fl2_open": (16, 2500, 6), "ow1_map3": (8, 1100, 8), "fl2_spec": (32, 1100, 9),
@@ -191,6 +228,8 @@ TRAJ = {  # cfg -> (n_envs, n_steps, seed)
     "ow2_allslip": (12, 1100, 14), "ow2_delay": (24, 800, 15), "ow3_slip": (8, 1100, 16),
     "fl2_randstart": (32, 1100, 17), "fl2_randstart_slip": (32, 1100, 18), "fl4_randstart_open": (16, 1100, 19),
     "ow1": (16, 1100, 0), "ow3": (12, 1100, 1), "ow2_final": (16, 1100, 2), "ow2_fail": (32, 600, 3),
+    "fl8_chain200": (4, 1100, 3), "fl1_chain200": (16, 1100, 3), "fl2_negpal": (16, 1100, 21),
+    "fl2_pal5": (16, 1100, 22), "fl1_qrm16": (8, 600, 23), "fl1_qrm17": (8, 600, 24),
 }
 EPISODES = {"fl2": (256, 2000, 7), "ow1": (32, 2200, 7)}
 
@@ -281,7 +320,8 @@ def make_env(cfg):
         else:
             ag.add_state_encoder(StateEncoderOfficeWorld(ag))
             ag.add_action_encoder(ActionEncoderOfficeWorld(ag))
-        ag.set_learning_algorithm(_QRMLearner())  # the wrapper then emits infos["qrm_experience"]
+        if cfg.get("record_qrm", True):
+            ag.set_learning_algorithm(_QRMLearner())  # the wrapper then emits infos["qrm_experience"]
         rm = build_rm_from_spec(ac["rm_spec"], cfg, detector) if "rm_spec" in ac else build_rm(ac["rm"], sym, detector)
         if "shaping_gamma" in cfg:
             with contextlib.redirect_stdout(io.StringIO()):
@@ -306,16 +346,20 @@ def run(cfg_name, n_envs, n_steps, seed, record_traj=True):
     ow = cfg["kind"] == "office_world"
     gamma = cfg.get("gamma", 1.0)
     acts = np.zeros((n_steps, A, n_envs), np.int8)
+    probe, _, _ = make_env(cfg)
+    # RM-state column: int8 as every fixture so far, int16 once a scenario's RM has indices past 127
+    q_dt = np.int8 if max(len(ag.get_reward_machine().state_indices) for ag in probe.agents) <= 127 else np.int16
     out = {k: np.zeros((n_steps, A, n_envs), dt) for k, dt in [
-        ("pos_x", np.int8), ("pos_y", np.int8), ("q", np.int8), ("reward", np.float64), ("shaping", np.float64),
+        ("pos_x", np.int8), ("pos_y", np.int8), ("q", q_dt), ("reward", np.float64), ("shaping", np.float64),
         ("renv", np.float64), ("rq", np.float64), ("term", np.bool_), ("trunc", np.bool_), ("active", np.bool_)]}
     env_done = np.zeros((n_steps, n_envs), np.bool_)
     # positions right after each reset (-1 where no reset preceded the step): pins random start positions
     reset_xy = np.full((n_steps, 2, A, n_envs), -1, np.int8)
     tcol = np.zeros((n_steps, n_envs), np.int16)
-    probe, _, _ = make_env(cfg)
     QX = max(len(ag.get_reward_machine().get_all_states()) - 1 for ag in probe.agents)
     # QRM experience tuples (rm_environment_wrapper.py:168-179): enc_s, a, r, enc_sn, done, s, q, sn, qn, hr
+    if not cfg.get("record_qrm", True):
+        QX = 0
     qrm = {k: np.full((n_steps, A, max(QX, 1), n_envs), -1 if dt != np.float64 else np.nan, dt) for k, dt in [
         ("qrm_s", np.int32), ("qrm_a", np.int32), ("qrm_r", np.float64), ("qrm_sn", np.int32), ("qrm_done", np.int8),
         ("qrm_pos", np.int32), ("qrm_q", np.int32), ("qrm_npos", np.int32), ("qrm_nq", np.int32),
@@ -378,7 +422,8 @@ def run(cfg_name, n_envs, n_steps, seed, record_traj=True):
                 need_reset = True
                 episode += 1
     ep = {k: np.asarray(v) for k, v in ep.items()}
-    out.update(qrm)
+    if cfg.get("record_qrm", True):
+        out.update(qrm)
     out["reset_xy"] = reset_xy
     return acts, out, env_done, tcol, ep
 

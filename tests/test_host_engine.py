@@ -14,7 +14,7 @@ from rmx import tables as T
 from rmx._capi import F_ACTIVE, F_TERM, F_TRUNC
 from rmx.engine import HostRMEnv
 from test_engine_gpu import RS_DERIVED, TRAJ
-from test_oracle_golden import check_mdp, check_qrm
+from test_oracle_golden import LIMIT_TRAJ, check_mdp, check_qrm
 
 REWARD_TOL = 1e-6
 
@@ -38,10 +38,12 @@ def _compare_stats(a, b):
 
 
 @pytest.mark.parametrize("qrm", [False, True])
-@pytest.mark.parametrize("name", TRAJ)
+@pytest.mark.parametrize("name", TRAJ + LIMIT_TRAJ)
 def test_host_engine_matches_reference_golden(name, qrm, configs, golden_dir):
-    """Every golden scenario (FrozenLake / OfficeWorld, quirks, specs, slip, delay, random starts) stepped by the host
-    handle, with and without the QRM columns, against the reference's recorded trajectories."""
+    """Every golden scenario (FrozenLake / OfficeWorld, quirks, specs, slip, delay, random starts, and the field-width
+    limits: 200-state chains, 8 agents, negative palettes) stepped by the host handle, with and without the QRM
+    columns, against the reference's recorded trajectories (the chain200 files record no QRM columns: with them the
+    host handle only has to step the same trajectory)."""
     g = dict(np.load(os.path.join(golden_dir, f"traj_{name}.npz")))
     tab = T.compile_scenario(configs[name])
     acts = g["actions"].astype(np.int32)
@@ -74,7 +76,7 @@ def test_host_engine_matches_reference_golden(name, qrm, configs, golden_dir):
     assert np.max(np.abs(r["renv"].astype(np.float64) - g["renv"])) <= REWARD_TOL
     sh = r["shaping"].astype(np.float64) if "shaping" in r else 0.0
     assert np.max(np.abs(r["reward"] + sh - (g["reward"] + g["shaping"]))) <= REWARD_TOL
-    if "qrm_s" in r:
+    if "qrm_s" in r and "qrm_s" in g:
         check_qrm(tab, r, g, acts, r["renv"])
 
 

@@ -12,7 +12,7 @@ import pytest
 import oracle as O
 from rmx import tables as T
 from rmx.engine import HostRMEnv
-from test_random_maps_gpu import CASES, SLIP_CASES, random_slip_tables, random_tables
+from test_random_maps_gpu import CASES, SLIP_CASES, case_tables, random_slip_tables, random_tables
 
 
 def _same_state(env, orc, what):
@@ -32,7 +32,7 @@ def _same_stats(env, orc):
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_host_random_world_vs_oracle(case):
-    tab = random_tables(*CASES[case])
+    tab = case_tables(case)
     N, Tn = 1500, 150
     env = HostRMEnv(tab, N, with_enc_state=True)
     orc = O.OracleEnv(tab, N)
@@ -125,3 +125,26 @@ def test_host_garbage_state_is_bounded(case, qrm):
     orc.rollout(3, 0, 40)
     for k in ("pos_x", "pos_y", "rm_q", "t"):
         np.testing.assert_array_equal(getattr(env, k), getattr(orc, k), err_msg=k)
+
+
+# ---- the limit worlds of tests/test_limits_gpu.py (8 agents, 250 RM states, 250 events, x / y up to 255, 4,096 cells)
+import test_limits_gpu as L  # noqa: E402
+from test_limits_cpu import _host_vs_reference  # noqa: E402
+
+
+@pytest.mark.parametrize("case", list(L.CASES))
+def test_host_limit_world_vs_oracle(case):
+    """The host step (its own index arithmetic over the generic blob's uint8 views) on every limit world; a host
+    handle's step_info is the host variant and zeros."""
+    env = _host_vs_reference(L.limit_world(case)[1], L.case_actions(case), L.case_reference(case))
+    info = env.step_info
+    assert info["variant"] == "host" and info["tables"] == "none"
+    assert all(v == 0 for k, v in info.items() if k not in ("variant", "tables", "rollout_layout"))
+
+
+@pytest.mark.parametrize("case", [c for c in L.RNG_CASES if not c.endswith("_skip")])
+def test_host_limit_world_slip_and_random_starts(case):
+    """Slip and random starts at 8 agents, at 250 RM states and over 255-wide / 255-high lakes, with the rng columns."""
+    tab, acts, ref = L.rng_reference(case, 300)
+    L.check_rng_liveness(case, tab, ref)
+    _host_vs_reference(tab, acts, ref, seed=31)

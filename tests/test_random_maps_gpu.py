@@ -19,17 +19,17 @@ pytestmark = pytest.mark.gpu
 REWARDS = (0.0, 1.0, 2.5, -1.0, 0.75)
 
 
-def random_rm(rng, Q, event_cells):
+def random_rm(rng, Q, event_cells, rewards=REWARDS):
     """A random RM over states s0..s{Q-1}: 1-3 outgoing transitions per state on random events."""
     tr = {}
     for q in range(Q):
         for _ in range(int(rng.integers(1, 4))):
             ev = None if rng.random() < 0.15 else tuple(int(v) for v in event_cells[rng.integers(len(event_cells))])
-            tr[(f"s{q}", ev)] = (f"s{int(rng.integers(Q))}", float(REWARDS[rng.integers(len(REWARDS))]))
+            tr[(f"s{q}", ev)] = (f"s{int(rng.integers(Q))}", float(rewards[rng.integers(len(rewards))]))
     return T.RewardMachineSpec(tr, initial_state="s0")
 
 
-def random_tables(seed, kind, W, H, A, Q, n_ev, shaping, wall_p=0.12, **extra):
+def random_tables(seed, kind, W, H, A, Q, n_ev, shaping, wall_p=0.12, rewards=REWARDS, reward_modifier=1.5, **extra):
     rng = np.random.default_rng(seed)
     cells = [(x, y) for y in range(H) for x in range(W)]
     perm = rng.permutation(len(cells))
@@ -43,12 +43,12 @@ def random_tables(seed, kind, W, H, A, Q, n_ev, shaping, wall_p=0.12, **extra):
             for nx, ny in ((x + 1, y), (x, y + 1)):
                 if nx < W and ny < H and rng.random() < wall_p:
                     walls += [((x, y), (nx, ny)), ((nx, ny), (x, y))]
-    rms = [random_rm(rng, Q, event_cells) for _ in range(A)]
+    rms = [random_rm(rng, Q, event_cells, rewards) for _ in range(A)]
     detectors = [[c for c in event_cells if rng.random() < 0.8] or event_cells[:1] for _ in range(A)]
     return T.compile_tables(kind, W, H, hazards, walls, starts, rms, detectors, hazard_penalty=-1.5,
                             wall_penalty=-0.25, hazard_fail=None if kind == T.FROZEN_LAKE else bool(seed % 2),
                             wall_fail=bool(seed % 3 == 0), gamma=0.95, shaping_gamma=0.9 if shaping else None,
-                            reward_modifier=1.5, max_t=60, **extra)
+                            reward_modifier=reward_modifier, max_t=60, **extra)
 
 
 CASES = {
@@ -58,7 +58,17 @@ CASES = {
     "fl_wide_global": (3, T.FROZEN_LAKE, 14, 14, 3, 5, 6, False),
     "ow_one_agent": (4, T.OFFICE_WORLD, 9, 7, 1, 4, 5, True),
     "fl_w300_generic": (5, T.FROZEN_LAKE, 300, 2, 2, 3, 4, False),
+    "fl_int_merged4": (6, T.FROZEN_LAKE, 7, 6, 3, 4, 4, False),
 }
+# Every case above pays reward_modifier 1.5 times rewards off the integer grid, which the 4-B merged records cannot
+# hold: their "merged4" rows run the 16-B records (asserted through step_info below).  fl_int_merged4 draws its rewards
+# from four integers under reward_modifier 1, so its default and merged4 rows do run the 4-B records.
+CASE_OPTIONS = {"fl_int_merged4": {"rewards": (-2.0, 0.0, 1.0, 3.0), "reward_modifier": 1.0}}
+
+
+def case_tables(case):
+    return random_tables(*CASES[case], **CASE_OPTIONS.get(case, {}))
+
 MODES = {  # env settings per kernel variant (round 5: the step's lost table modes and layouts were removed)
     "default": {},
     "global": {"RMX_FAST_TABLES": "global"},
@@ -93,9 +103,20 @@ def test_random_world_vs_oracle(case, mode, torch, monkeypatch):
         monkeypatch.delenv(k, raising=False)
     for k, v in MODES[mode].items():
         monkeypatch.setenv(k, v)
-    tab = random_tables(*CASES[case])
+    from test_limits_gpu import expected_info
+
+    tab = case_tables(case)
     N, Tn = 1500, 150
     env = VecRMEnv(tab, N, with_enc_state=True)
+    # the kernel configuration in effect (rmx_step_info) against the selection rules restated from the tables: a forced
+    # table mode that silently fell back shows here
+    info, want = env.step_info, expected_info(tab, N, MODES[mode])
+    assert info == want, {k: (info[k], want[k]) for k in want if info[k] != want[k]}
+    if info["variant"] == "fast" and mode in ("merged4", "merged4_nt"):  # what the merged4 rows really run
+        assert info["tables"] == ("merged4" if case == "fl_int_merged4" else "merged"), (case, mode, info)
+        assert info["record_bytes"] == (4 if case == "fl_int_merged4" else 16)
+    if case == "fl_int_merged4" and mode == "default":
+        assert (info["tables"], info["record_bytes"], info["merged_sections"]) == ("merged4", 4, 3)
     if case == "fl_w300_generic":
         assert env.step_variant == ("lane_per_agent" if mode == "generic_lpe" else "generic")  # W > 255: not fast
     elif mode.startswith("generic"):

@@ -146,3 +146,37 @@ def test_dense_rm_table_semantics():
     assert np.all(sc.rm_reward[:, :, 0] == 0)
     A_id = sc.event_cells.index((4, 4)) + 1
     assert sc.next_q[0, 0, A_id] == 1 and sc.rm_reward[0, 0, A_id] == 10
+
+
+def _wide_rm(n_states, cells):
+    """s000 -> s001 -> ... one transition per state on the cells in turn (zero-padded names: index == k)."""
+    return T.RewardMachineSpec({(f"s{k:03d}", cells[k % len(cells)]): (f"s{k + 1:03d}", float(k % 7 - 3))
+                                for k in range(n_states - 1)})
+
+
+def test_tables_keep_the_eighth_bit():
+    """Q = 255 and E = 255: cell_event, next_q and qrm_states are unsigned bytes that hold 128..254 unchanged."""
+    W, H = 16, 16
+    cells = [(x, y) for x in range(W) for y in range(H)][:254]  # x-major = sorted order: event id k + 1 at cells[k]
+    rm = _wide_rm(255, cells)
+    tab = T.compile_tables(T.FROZEN_LAKE, W, H, [], (), [(15, 15)], [rm], [cells])
+    assert (tab.n_rm_states, tab.n_events) == (255, 255)
+    for arr in (tab.cell_event, tab.next_q, tab.qrm_states):
+        assert arr.dtype == np.uint8
+    for k, (x, y) in enumerate(cells):
+        assert int(tab.cell_event[0, y * W + x]) == k + 1
+    for k in range(254):
+        ev = k % 254 + 1
+        assert int(tab.next_q[0, k, ev]) == k + 1  # the transition, 254 included
+        assert int(tab.next_q[0, k, ev % 254 + 1]) == k  # a missing one: the self loop, 128..253 included
+    np.testing.assert_array_equal(tab.qrm_states[0].astype(np.int64), np.arange(254))
+    assert int(tab.final_q[0]) == 254 and int(tab.cell_event.max()) == 254 and int(tab.next_q.max()) == 254
+
+
+def test_tables_refuse_256_states_or_events():
+    W, H = 16, 16
+    cells = [(x, y) for x in range(W) for y in range(H)]
+    with pytest.raises(ValueError, match="uint8 index range"):  # Q = 256
+        T.compile_tables(T.FROZEN_LAKE, W, H, [], (), [(0, 0)], [_wide_rm(256, cells[:4])], [cells[:4]])
+    with pytest.raises(ValueError, match="uint8 index range"):  # E = 256
+        T.compile_tables(T.FROZEN_LAKE, W, H, [], (), [(0, 0)], [_wide_rm(3, cells[:4])], [cells[:255]])
