@@ -262,6 +262,12 @@ int rmx_step_report_fused(const rmx_handle* h);
  * every window after a failed one.  A window fails (RMX_E_HIP, its results undefined) when the queue faults or does
  * not complete within 60 s; the queue is then inactivated (none of its packets keeps running) and retired for the
  * process.
+ * Inside a queue window the steps may hand the state to each other in a private layout of the handle's own and skip
+ * outputs that a later step of the same window overwrites (reward, env_done and the optional per-step columns of
+ * every step but the last): the caller's buffers are read by the window's first step and written by its last, and
+ * hold after the call exactly what the n_steps calls would have left.  A failed window leaves them undefined, as
+ * before.  The default deterministic step (no slip, fixed starts, no QRM outputs, below 1M envs) takes this form for
+ * n_steps >= 2; RMX_SEQ_PACKED=0 in the environment at rmx_create keeps the window of n_steps column-to-column steps.
  * rmx_queue_counters: that queue's windows, kernel-argument uploads and packets so far for the handle's device.
  * rmx_queue_info: out[0..n) of RMX_QUEUE_INFO_N values: [0] windows, [1] uploads, [2] packets (as above), [3] windows
  * of the device served on a stream, [4] the device queue's state (RMX_QUEUE_*), [5] how the handle's last
@@ -269,6 +275,8 @@ int rmx_step_report_fused(const rmx_handle* h);
  * the recording and uploads nothing). */
 int rmx_step_seq(rmx_handle* h, const int32_t* actions_dev, int64_t action_stride, int32_t n_steps, int autoreset,
                  double* stats_out_dev, void* hip_stream);
+/* 1 if the handle's last rmx_step_seq ran on the queue as a packed window (the private layout above), else 0. */
+int rmx_seq_packed(const rmx_handle* h);
 int rmx_queue_counters(const rmx_handle* h, int64_t* out3);
 #define RMX_QUEUE_INFO_N 7
 #define RMX_QUEUE_UNUSED 0      /* not set up yet (no window on this device so far) */

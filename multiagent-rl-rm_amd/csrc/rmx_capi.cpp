@@ -69,6 +69,13 @@ struct rmx_handle {
   int seq_autoreset = -1;
   uint64_t seq_key = 0;  // 0: nothing recorded
   bool queue_off = false;  // RMX_QUEUE=0 at rmx_create: rmx_step_seq always takes the stream path
+  // packed windows (rmx_layout.h "the packed record"): RMX_SEQ_PACKED=0 at rmx_create turns them off; the record
+  // buffer is allocated by the first eligible window (a failed allocation is remembered: windows stay unpacked)
+  bool seq_packed_off = false;
+  bool pk_failed = false;
+  bool pk_refused = false;  // the kernel side did not take the window kernel for this handle: not tried again
+  uint32_t* d_pk = nullptr;
+  bool seq_is_packed = false;  // the recorded window (seq) is a packed one
   int seq_dispatch = RMX_SEQ_NONE;  // how the last rmx_step_seq ran
   int64_t seq_recordings = 0;       // windows recorded (a repeated identical call reuses the last one)
   int device = 0;
@@ -337,6 +344,7 @@ rmx::FastParams fast_params(const rmx_handle* h) {
   p.err = h->d_err;
   p.diag = h->diag;
   p.stamps = h->d_stamps;
+  p.pk = h->d_pk;  // (in the block rmx_step_seq compares: a window recorded before the buffer existed is recorded again)
   if (c.stochastic || c.random_starts) {  // slip and / or FrozenLake random starts on the fast path
     p.slip = (c.stochastic ? rmx::kRngSlip : 0) | (c.random_starts ? rmx::kRngStarts : 0) |
              (h->seed_fixed ? rmx::kRngFixedSeed : 0);
@@ -749,6 +757,7 @@ int rmx_create(const rmx_config* cfg, rmx_handle** out) {
   h->cfg = *cfg;
   h->device = cfg->device;
   if (const char* qv = std::getenv("RMX_QUEUE")) h->queue_off = std::strcmp(qv, "0") == 0;
+  if (const char* pv = std::getenv("RMX_SEQ_PACKED")) h->seq_packed_off = std::strcmp(pv, "0") == 0;
   if (const char* b = std::getenv("RMX_BLOCK")) {
     int v = std::atoi(b);
     if (v == 64 || v == 128 || v == 256) h->block = v;
@@ -986,6 +995,7 @@ void rmx_destroy(rmx_handle* h) {
   (void)hipFree(h->d_start_ws);
   (void)hipFree(h->d_nx);
   (void)hipFree(h->d_rsc);
+  (void)hipFree(h->d_pk);
   delete h;
 }
 
@@ -1160,20 +1170,49 @@ int rmx_step_report(rmx_handle* h, const int32_t* actions_dev, int autoreset, do
 
 int rmx_step_report_fused(const rmx_handle* h) { return h && h->bound && report_fuses(h) ? 1 : 0; }
 
+// Packed windows serve the handles whose step is the default deterministic one: the merged-table step_fast_kernel with
+// caller actions, the kSkipRare store set and per-env statistics slots (below 1M envs), no QRM outputs, no slip, fixed
+// starts.  Everything else (and RMX_SEQ_PACKED=0, and a handle whose record buffer could not be allocated) keeps the
+// window of K column-to-column steps.
+static bool seq_packs(const rmx_handle* h) {
+  const int tm = h->fast_tables;
+  // (below 1M envs also keeps the record's byte offsets, (3A + 1) * N * 4, far inside the buffer descriptor's 32 bits)
+  return !h->seq_packed_off && !h->pk_failed && !h->pk_refused && h->cfg.n_envs < kFastWaveStatsMinEnvs &&
+         rmx::pk_bytes(h->cfg.n_agents, (size_t)h->cfg.n_envs) < ((size_t)1 << 31) && fast_applies(h) && !h->cfg.stochastic && !h->cfg.random_starts &&
+         !h->buf.qrm_s && !h->fast_wave_stats && h->fast_skip == rmx::kSkipRare &&
+         (tm == rmx::kTblMerged4 || tm == rmx::kTblMerged) && h->cfg.n_agents <= rmx::kFastMaxAgents;
+}
+
+// The record buffer of a handle's packed windows, allocated by its first one; false (remembered) when it cannot be
+static bool seq_pack_buffer(rmx_handle* h) {
+  if (h->d_pk) return true;
+  if (hipMalloc(&h->d_pk, rmx::pk_bytes(h->cfg.n_agents, (size_t)h->cfg.n_envs)) != hipSuccess) {
+    (void)hipGetLastError();  // not an error of the call: the window runs unpacked
+    h->d_pk = nullptr;
+    h->pk_failed = true;
+    return false;
+  }
+  return true;
+}
+
 // The K launches rmx_step / rmx_step_report would issue, recorded (rmx::tl_capture) instead; false when the handle's
-// step is not the thread-per-env step_fast_kernel.
+// step is not the thread-per-env step_fast_kernel.  packed (K >= 2): the same K packets as step_fast_kernel_win's I/O
+// modes, the first one reading the columns, the last one writing them, the ones between on the handle's records.
 static bool record_seq(rmx_handle* h, const int32_t* actions, int64_t stride, int32_t K, int autoreset,
-                       double* stats_out, bool fused) {
+                       double* stats_out, bool fused, bool packed) {
   h->seq.resize((size_t)K);
   for (int32_t k = 0; k < K; ++k) {
     const int32_t* a = actions + (size_t)k * (size_t)stride;
     const bool rpt = fused && k == K - 1;
-    const rmx::FastParams fp = rpt ? report_fp(h, a, autoreset, stats_out) : step_fp(h, a, 0, 0, autoreset);
+    rmx::FastParams fp = rpt ? report_fp(h, a, autoreset, stats_out) : step_fp(h, a, 0, 0, autoreset);
+    if (packed) fp.pk_io = k == 0 ? rmx::kIoColsToPk : (k == K - 1 ? rmx::kIoPkToCols : rmx::kIoPkToPk);
     rmx::StepCapture cap{&h->seq[(size_t)k], false};
     rmx::tl_capture = &cap;
     (void)rmx::launch_step_fast(fp, 0, h->cfg.kind, nullptr);
     rmx::tl_capture = nullptr;
     if (!cap.ok) return false;
+    // the kernel side's dispatch must have taken the window kernel: a mixed window would read columns nobody wrote
+    if (packed && !std::strstr(h->seq[(size_t)k].symbol, "step_fast_kernel_win")) return false;
   }
   return true;
 }
@@ -1217,13 +1256,22 @@ static int step_seq(rmx_handle* h, const int32_t* actions_dev, int64_t action_st
   }
   // the window recorded by the previous call is this one when the parameter block and the arguments agree
   // (fast_params zero-fills the block and FastParams has no padding, rmx_internal.h: a byte compare is a field one)
-  const rmx::FastParams base = fast_params(h);
+  const bool packed = n_steps >= 2 && seq_packs(h) && seq_pack_buffer(h);
+  rmx::FastParams base = fast_params(h);  // (with the record buffer, once there is one)
   const bool same = h->seq_key && h->seq_actions == actions_dev && h->seq_stride == action_stride &&
                     h->seq_k == n_steps && h->seq_autoreset == (autoreset ? 1 : 0) && h->seq_out == stats_out_dev &&
                     std::memcmp(&base, &h->seq_base, sizeof(base)) == 0;
   if (!same) {
     h->seq_key = 0;
-    if (!record_seq(h, actions_dev, action_stride, n_steps, autoreset, stats_out_dev, fused)) {
+    h->seq_is_packed = packed && record_seq(h, actions_dev, action_stride, n_steps, autoreset, stats_out_dev, fused, true);
+    if (packed && !h->seq_is_packed) {  // this handle's dispatch goes elsewhere: no record buffer, no second try
+      h->pk_refused = true;
+      (void)hipFree(h->d_pk);
+      h->d_pk = nullptr;
+      base = fast_params(h);
+    }
+    if (!h->seq_is_packed &&
+        !record_seq(h, actions_dev, action_stride, n_steps, autoreset, stats_out_dev, fused, false)) {
       rmx::queue_note_stream(h->device);
       return on_stream(RMX_SEQ_STREAM_KERNEL);
     }
@@ -1265,6 +1313,10 @@ int rmx_step_seq(rmx_handle* h, const int32_t* actions_dev, int64_t action_strid
     if (h) h->seq_key = 0;
     return fail(RMX_E_HIP, std::string("rmx_step_seq: ") + e.what());
   }
+}
+
+int rmx_seq_packed(const rmx_handle* h) {
+  return h && !h->host && h->seq_dispatch == RMX_SEQ_QUEUE && h->seq_key && h->seq_is_packed ? 1 : 0;
 }
 
 int rmx_queue_counters(const rmx_handle* h, int64_t* out3) {

@@ -229,6 +229,11 @@ struct FastParams {
   // restore or a rebind: a reset copies the whole cached generator.
   int32_t rs_dirty;
   int32_t pad5;
+  // rmx_step_seq's packed window (rmx_layout.h "the packed record"): the handle's record buffer (or NULL), and this
+  // launch's I/O mode kIo* (kIoCols everywhere but in a packed window's packets: step_fast_kernel_win)
+  uint32_t* pk;  // [3A + 1][N]
+  int32_t pk_io;
+  int32_t pad7;
 };
 // rmx_step_seq reuses a recorded window while the new parameter block equals the recorded one byte for byte (and
 // the queue diffs kernel arguments byte for byte): that is a field compare only if FastParams has no implicit padding.
@@ -243,7 +248,7 @@ struct FastParams {
    X(pad3) X(stamps) X(rpt_out) X(rpt_partial) X(rpt_ticket) X(rpt_cs) X(rpt_n_slab) X(slip_n) X(slip_out) \
    X(slip_thr) X(slip_uniform) X(pad4) X(slip_pack) X(seed_scale) X(seed_env_stride) X(seed_episode_stride) \
    X(base_seed) X(rng) X(episode) X(slip) X(n_free) X(free_cells) X(start_ws) X(nx_rng) X(nx_idx) X(nx_ep) \
-   X(rs_jump) X(rs_cells) X(rs_rng) X(rs_dirty) X(pad5)
+   X(rs_jump) X(rs_cells) X(rs_rng) X(rs_dirty) X(pad5) X(pk) X(pk_io) X(pad7)
 #define RMX_FP_FIELD_BYTES(f) +sizeof(FastParams::f)
 constexpr size_t kFastParamsFieldBytes = 0 RMX_FAST_PARAMS_FIELDS(RMX_FP_FIELD_BYTES);
 #undef RMX_FP_FIELD_BYTES

@@ -28,6 +28,7 @@ EXPORTS = (
     "rmx_get_state", "rmx_set_state", "rmx_step_report", "rmx_step_report_fused", "rmx_reset_sync", "rmx_step_sync",
     "rmx_step_sync_begin", "rmx_sync_wait", "rmx_sync_end", "rmx_step_seq", "rmx_queue_counters", "rmx_queue_info",
     "rmx_code_object_check", "rmx_device_count", "rmx_queue_timing", "rmx_queue_times", "rmx_step_info",
+    "rmx_seq_packed",
 )
 SYNC_MAX_ENVS = 256  # RMX_SYNC_MAX_ENVS
 QUEUE_INFO_N = 7  # RMX_QUEUE_INFO_N
@@ -49,8 +50,8 @@ ABI_VERSION = 12  # include/rmx.h RMX_ABI_VERSION
 # The sources whose SHA-256 (concatenated in this order) librmx.so reports through rmx_build_info(): the same
 # list as RMX_HASHED in csrc/Makefile (tests/test_capi.py checks that they agree).
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
-HASHED_SOURCES = ("rmx_kernels.hip", "rmx_fast.hip", "rmx_sync.hip", "rmx_capi.cpp", "rmx_queue.cpp", "rmx_tables.cpp",
-                  "rmx_comd.cpp", "rmx_build_info.cpp", "rmx_internal.h", "rmx_layout.h", "rmx_host.h", "rmx_device.h",
+HASHED_SOURCES = ("rmx_kernels.hip", "rmx_fast.hip", "rmx_fast_step.inc", "rmx_sync.hip", "rmx_capi.cpp",
+                  "rmx_queue.cpp", "rmx_tables.cpp", "rmx_comd.cpp", "rmx_build_info.cpp", "rmx_internal.h", "rmx_layout.h", "rmx_host.h", "rmx_device.h",
                   "rmx_generic.h", "rmx_comd.h", "rmx_hoststep.cpp", "rmx_hoststep.h", "../../include/rmx.h",
                   "Makefile")
 
@@ -203,6 +204,7 @@ def load_library(path: str = None, check_source: bool = True):
         "rmx_step_variant": (C.c_int, [vp]),
         "rmx_step_report": (C.c_int, [vp, vp, C.c_int, vp, vp]),
         "rmx_step_report_fused": (C.c_int, [vp]),
+        "rmx_seq_packed": (C.c_int, [vp]),
         "rmx_step_seq": (C.c_int, [vp, vp, C.c_int64, C.c_int32, C.c_int, vp, vp]),
         "rmx_queue_timing": (C.c_int, [vp, C.c_int]),
         "rmx_queue_times": (C.c_int, [vp, vp, C.c_int64, C.POINTER(C.c_int64)]),

@@ -4,6 +4,8 @@
 //   copy_dw   : the step kernel's exact traffic pattern (per env: t r/w, per agent 5 cols r/w + action r
 //               + reward w, env_done w), dword per lane, no compute
 //   copy_dw4  : same bytes, 4 envs per thread with 16-B loads/stores
+//   copy_window* : the interior step of a packed rmx_step_seq window (no reward / env_done store) in the candidate
+//               record layouts: 16-B units per agent, field-major units + a t column, 4-B columns
 // Build: hipcc -O3 --offload-arch=gfx950 floor_bench.hip -o floor_bench
 #include <execinfo.h>
 #include <fcntl.h>
@@ -254,6 +256,105 @@ __global__ void __launch_bounds__(64) copy_cfg_gather(Cols p, int* shaping, cons
   p.done[e] = (unsigned char)(t ^ g[0]);
 }
 
+// The interior step of a packed rmx_step_seq window (packed -> packed): one 16-B unit per agent, each unit a column
+// of its own ([A][N] uint4: {x | y << 8 | q << 16, flags, ep_ret, t}), still one env per lane; per lane A 16-B loads
+// and A action loads in, A 16-B sc1 stores out, no reward and no env_done store.  Against copy_cfg<A> (the column
+// layout's floor) on the same box.
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+template <int A>
+__global__ void __launch_bounds__(64) copy_window(Cols p, u32x4_t* units) {
+  long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= p.N) return;
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(units, 0, (int)(p.N * A * 16), 0x00020000);
+  u32x4_t v[A];
+  int act[A];
+#pragma unroll
+  for (int a = 0; a < A; ++a) {
+    v[a] = __builtin_amdgcn_raw_buffer_load_b128(r, (unsigned)e * 16u, (unsigned)(a * p.N) * 16u, 0);
+    act[a] = p.act[a * p.N + e];
+  }
+#pragma unroll
+  for (int a = 0; a < A; ++a) {
+    u32x4_t w = v[a];
+    w[0] += (unsigned)act[a];
+    w[1] += (unsigned)act[a];
+    w[2] ^= (unsigned)act[a];
+    w[3] += 1u;
+    __builtin_amdgcn_raw_buffer_store_b128(w, r, (unsigned)e * 16u, (unsigned)(a * p.N) * 16u, 16);
+  }
+}
+// copy_window with default-policy stores (AUX 0) or 256-thread workgroups: is it the store policy or the block shape?
+template <int A, int AUX, int BLK>
+__global__ void __launch_bounds__(BLK) copy_window_v(Cols p, u32x4_t* units) {
+  long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= p.N) return;
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(units, 0, (int)(p.N * A * 16), 0x00020000);
+  u32x4_t v[A];
+  int act[A];
+#pragma unroll
+  for (int a = 0; a < A; ++a) {
+    v[a] = __builtin_amdgcn_raw_buffer_load_b128(r, (unsigned)e * 16u, (unsigned)(a * p.N) * 16u, 0);
+    act[a] = p.act[a * p.N + e];
+  }
+#pragma unroll
+  for (int a = 0; a < A; ++a) {
+    u32x4_t w = v[a];
+    w[0] += (unsigned)act[a];
+    w[1] += (unsigned)act[a];
+    w[2] ^= (unsigned)act[a];
+    w[3] += 1u;
+    __builtin_amdgcn_raw_buffer_store_b128(w, r, (unsigned)e * 16u, (unsigned)(a * p.N) * 16u, AUX);
+  }
+}
+// The window's words as 4-B columns instead of 16-B units (W words per agent loaded, S of them stored, plus t and the
+// actions): W = 3, S = 3 is the packed record word by word (cell, flags, ep_ret); S = 2 leaves the rarely changing
+// ep_ret word unstored; W = 5, S = 3 is today's column layout with only the dead reward / env_done stores dropped.
+template <int A, int W, int S>
+__global__ void __launch_bounds__(64) copy_window_dw(Cols p) {
+  long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= p.N) return;
+  int t = p.t[e];
+  int v[A][W + 1];
+#pragma unroll
+  for (int a = 0; a < A; ++a) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) v[a][k] = p.c[k][a * p.N + e];
+    v[a][W] = p.act[a * p.N + e];
+  }
+  st_sc1(p.t, e, t + 1);
+#pragma unroll
+  for (int a = 0; a < A; ++a) {
+    int x = v[a][W];
+#pragma unroll
+    for (int k = S; k < W; ++k) x ^= v[a][k];
+#pragma unroll
+    for (int k = 0; k < S; ++k) st_sc1(p.c[k], a * p.N + e, v[a][k] + x);
+  }
+}
+// The same window step with `t` as a 4-B column of its own and the A agents' words field-major in U = 3 units
+// (A = 4: 13 words as 3 x 16 B + 4 B instead of 4 x 16 B).
+template <int A, int U>
+__global__ void __launch_bounds__(64) copy_window_tcol(Cols p, u32x4_t* units) {
+  long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= p.N) return;
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(units, 0, (int)(p.N * U * 16), 0x00020000);
+  u32x4_t v[U];
+  int act[A];
+  const int t = p.t[e];
+#pragma unroll
+  for (int u = 0; u < U; ++u) v[u] = __builtin_amdgcn_raw_buffer_load_b128(r, (unsigned)e * 16u, (unsigned)(u * p.N) * 16u, 0);
+#pragma unroll
+  for (int a = 0; a < A; ++a) act[a] = p.act[a * p.N + e];
+  st_sc1(p.t, e, t + 1);
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    u32x4_t w = v[u];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) w[a] += (unsigned)act[a % A];
+    __builtin_amdgcn_raw_buffer_store_b128(w, r, (unsigned)e * 16u, (unsigned)(u * p.N) * 16u, 16);
+  }
+}
+
 __global__ void __launch_bounds__(256) copy_dw4(Cols p) {
   long long e4 = ((long long)blockIdx.x * blockDim.x + threadIdx.x);
   if (e4 * 4 >= p.N) return;
@@ -408,6 +509,32 @@ int main(int argc, char** argv) {
       };
       printf(", \"copy_cfg2_us\": %.3f, \"copy_cfg3_us\": %.3f, \"copy_cfg4_us\": %.3f, \"copy_cfg5_us\": %.3f",
              cfg(copy_cfg<2, false>, q), cfg(copy_cfg<1, false>, q), cfg(copy_cfg<4, false>, q), cfg(copy_cfg<3, true>, q));
+      {  // the packed window's interior step (16-B units, no reward / env_done store), same chain, same box
+        u32x4_t* units = nullptr;
+        CK(hipMalloc(&units, 16 * 4 * N));
+        CK(hipMemset(units, 0, 16 * 4 * N));
+        auto win = [&](auto kern) {
+          return time_chain([&](hipStream_t st) { hipLaunchKernelGGL(kern, dim3(g64), dim3(64), 0, st, q, units); }, K, s);
+        };
+        printf(", \"copy_window_cfg2_us\": %.3f, \"copy_window_cfg4_us\": %.3f, \"copy_window_cfg4_tcol_us\": %.3f",
+               win(copy_window<2>), win(copy_window<4>), win(copy_window_tcol<4, 3>));
+        auto win256 = [&](auto kern) {
+          return time_chain([&](hipStream_t st) { hipLaunchKernelGGL(kern, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, q, units); }, K, s);
+        };
+        auto windw = [&](auto kern) {
+          return time_chain([&](hipStream_t st) { hipLaunchKernelGGL(kern, dim3(g64), dim3(64), 0, st, q); }, K, s);
+        };
+        printf(", \"copy_window_cfg2_aux0_us\": %.3f, \"copy_window_cfg2_b256_us\": %.3f", win(copy_window_v<2, 0, 64>),
+               win256(copy_window_v<2, 16, 256>));
+        printf(", \"copy_window_dw33_cfg2_us\": %.3f, \"copy_window_dw32_cfg2_us\": %.3f, \"copy_window_dw53_cfg2_us\": %.3f",
+               windw(copy_window_dw<2, 3, 3>), windw(copy_window_dw<2, 3, 2>), windw(copy_window_dw<2, 5, 3>));
+        printf(", \"copy_window_dw33_cfg4_us\": %.3f, \"copy_window_dw32_cfg4_us\": %.3f, \"copy_window_dw53_cfg4_us\": %.3f",
+               windw(copy_window_dw<4, 3, 3>), windw(copy_window_dw<4, 3, 2>), windw(copy_window_dw<4, 5, 3>));
+        // the column floors again, after the window forms (same-box drift check)
+        printf(", \"copy_cfg2_again_us\": %.3f, \"copy_cfg4_again_us\": %.3f", cfg(copy_cfg<2, false>, q),
+               cfg(copy_cfg<4, false>, q));
+        CK(hipFree(units));
+      }
       int* tbl = nullptr;  // the gather table: small words, zero-initialised then filled with a pattern
       CK(hipMalloc(&tbl, sizeof(int) * kGatherEntries));
       {
