@@ -348,6 +348,69 @@ int rmx_step_variant(const rmx_handle* h);
 #define RMX_TABLES_MERGED4 3
 int rmx_step_info(const rmx_handle* h, int64_t* out, int32_t n);
 
+/* ---- tabular Q-learning / QRM learners fused into the step ------------------------------------------------------
+ * QLearning.update behind AgentRL.update_policy (learning_algorithms/qlearning.py:41-110, multi_agent/agent_rl.py:
+ * 117-192) as the runners call it for every agent after every step (frozen_lake_main.py:345-376, office_main.py:
+ * 1709-1749): one independent learner per (agent a, env e), i.e. N replicas of the runner's experiment.
+ * Tables: caller-owned float64 q[A][N][S_max][4] and (optional) visits of the same shape, S_max = W*H*max_a enc_nq[a]
+ * (rmx_learn_states); q[a][e] is that learner's q_table as the reference holds it ([state][action], state =
+ * (y*W + x)*enc_nq[a] + rm index), rows past W*H*enc_nq[a] are never touched.  The caller fills q with qtable_init
+ * and visits with 0; a device handle takes device pointers (16-byte aligned), a host handle host pointers.  Each table
+ * is A * N * S_max * 4 doubles (N = cfg.n_envs): rmx_learn_bind cannot check the extent, and the learn step indexes
+ * all of [A][N][S_max][4].
+ * update_q (qlearning.py:70-79), each step one IEEE float64 operation, never fused:
+ *   visits[s][k] += 1 (when bound); lr = learning_rate, or 1/visits[s][k] (correctly rounded) when learning_rate == 0
+ *   (the reference's learning_rate=None; its constructor cannot be called with it, qlearning.py:37, its update can);
+ *   maxq = 0 when done, else max(q[sn][0..3]);  a = (1-lr)*cur; b = gamma*maxq; c = r + b; d = lr*c; q[s][k] = a + d.
+ * Experiences of one agent-step, strictly in order on the one table (a later one reads what an earlier one wrote):
+ *   use_qrm: one update_q per RM state j of get_all_states()[:-1] (qlearning.py:82-106 over rm_environment_wrapper.py:
+ *     140-183; the tuples of the qrm_* columns): s = prev_cell*nQ + q_j, sn = cell*nQ + nq_j, done = env_term ||
+ *     nq_j == final, r = (double)Renv + (double)rq_j (the raw RM reward, rm_environment_wrapper.py:171), and with
+ *     use_rsh r += gamma*phi[nq_j] - phi[q_j] in float64 (qlearning.py:93-105; gamma is the learner's);
+ *   else one update_q: s = encode(pre-step position, pre-step RM state) (the reset state when the step auto-reset
+ *     first), sn = encode(post-step ...), r = (double)Renv + (double)reward_modifier*(double)RQ, done = terminated ||
+ *     (trunc_is_terminal && truncated): trunc_is_terminal = 1 is the FrozenLake runner (frozen_lake_main.py:359), 0 the
+ *     OfficeWorld runner (office_main.py:1733).
+ * Every agent updates every step, inactive and RM-final ones included, as the runners do.  An action without a table
+ * column (RMX_WAIT, or an invalid one, reported as rmx_step reports it) is stepped and updates nothing.
+ * use_rsh without use_qrm is refused: the reference's own non-QRM shaping looks a label-keyed dict up by RM index
+ * (agent_rl.py:158-165, qlearning.py:60-66), which is not reproduced.  The learn step serves deterministic dynamics
+ * and fixed starts: a config with cfg.stochastic or cfg.random_starts is refused.
+ * Bit-exactness: q equals the reference's bit for bit whenever every reward, penalty and reward_modifier of the
+ * scenario is a float32 value (the engine stores them as float32).
+ * The engine's policy (rmx_learn_step_policy; its own, not numpy's stream; independent of the sharding), chosen after
+ * the auto-reset from the row of the state the step is about to leave, for agent i of global env e at t_global:
+ *   h0 = splitmix64(seed ^ (((t_global*N_global + e)*A + i) * 0x9E3779B97F4A7C15))  (rmx_fill_actions' value before
+ *   its >> 62), h1 = splitmix64(h0), h2 = splitmix64(h1); explore iff (h1 >> 11) * 2^-53 < epsilon, with action
+ *   h0 >> 62; else greedy: the row's maxima by float64 equality with the row maximum, in index order, maximum number
+ *   ((h2 >> 32) * n_max) >> 32 (qlearning.py:137-143 with the engine's draw).  RMX_LEARN_BEST: the first maximum
+ *   (np.argmax, qlearning.py:116-117).
+ * Each learn step is ONE launch on the caller's stream: auto-reset, action choice, step, update.  It leaves every
+ * bound column (enc_state and the QRM columns included) and the episode statistics as rmx_step with the same actions
+ * leaves them (the statistics through the generic kernels' per-wave slots: the integer ones equal, the return sum in
+ * that kernel's association).  Without RMX_LEARN_UPDATE the step is an evaluation step: the tables are only read.
+ * rmx_learn_bind copies phi (host [A][Q], Q = cfg.n_rm_states; required with use_rsh) and keeps q / visits
+ * (visits: NULL unless learning_rate == 0 or the counts are wanted).  RMX_E_INVALID with a message, before any device
+ * work: a NULL handle / config / q, gamma or learning_rate not finite or negative, no enc_nq, use_qrm with
+ * n_qrm_max == 0, use_rsh without use_qrm or phi, 1/visits without visits, cfg.stochastic / cfg.random_starts,
+ * epsilon outside [0, 1], unknown flags.  A learn step before rmx_bind or rmx_learn_bind: RMX_E_STATE.
+ * Not served: rmx_step_seq windows (learn steps are stream launches), the dict API, the tables in rmx_get_state
+ * (they are the caller's). */
+typedef struct rmx_learn_config {
+  double gamma, learning_rate /* 0: 1/visits */;
+  int32_t use_qrm, use_rsh, trunc_is_terminal, reserved;
+  const double* phi; /* host [A][Q], required with use_rsh; copied */
+} rmx_learn_config;
+#define RMX_LEARN_UPDATE 1
+#define RMX_LEARN_BEST 2
+int rmx_learn_states(const rmx_handle* h, int64_t* s_max);
+int rmx_learn_bind(rmx_handle* h, const rmx_learn_config* cfg, double* q, double* visits);
+/* rmx_step with the caller's actions, then the update */
+int rmx_learn_step(rmx_handle* h, const int32_t* actions, int autoreset, void* hip_stream);
+/* the policy's actions (written to actions_out [A][N] unless NULL), the step, and with RMX_LEARN_UPDATE the update */
+int rmx_learn_step_policy(rmx_handle* h, double epsilon, int flags, uint64_t seed, int64_t t_global, int autoreset,
+                          int32_t* actions_out, void* hip_stream);
+
 /* Synchronise and report kernel-side errors (e.g. RMX_E_ACTION), then clear them. */
 int rmx_check_errors(rmx_handle* h);
 

@@ -158,6 +158,11 @@ struct rmx_handle {
   int sy_oneshot = 0;       // RMX_SYNC=launch: one launch per request (A/B of the resident workgroup)
   uint64_t sy_idle_ticks = 0, sy_life_ticks = 0;
   bool sy_enc = false;  // the records' enc_state word is meaningful (every agent has an encoder stride)
+  // the learner bound by rmx_learn_bind to a device handle (a host handle's is host->learn / host->learn_on): the
+  // caller's tables and the handle's device copy of phi
+  rmx::LearnParams learn{};
+  bool learn_on = false;
+  double* d_phi = nullptr;
 #ifdef RMX_DIAG
   std::chrono::steady_clock::time_point sy_t_post;  // diag: when the last request was posted
   double sy_wait_ns = 0;                             // diag: post -> acknowledgement seen by the host
@@ -996,6 +1001,7 @@ void rmx_destroy(rmx_handle* h) {
   (void)hipFree(h->d_nx);
   (void)hipFree(h->d_rsc);
   (void)hipFree(h->d_pk);
+  (void)hipFree(h->d_phi);
   delete h;
 }
 
@@ -1120,6 +1126,112 @@ static int do_step(rmx_handle* h, const int32_t* actions, int hashed, uint64_t s
 
 int rmx_step(rmx_handle* h, const int32_t* actions_dev, int autoreset, void* stream) {
   return do_step(h, actions_dev, 0, 0, 0, autoreset, stream);
+}
+
+// ---- the tabular Q-learning / QRM learner fused into the step (rmx_learn.h, rmx_learn.hip) ----------------------
+int rmx_learn_states(const rmx_handle* h, int64_t* s_max) {
+  if (!h || !s_max) return fail(RMX_E_INVALID, "handle or s_max is NULL");
+  int32_t m = 0;
+  for (int a = 0; a < h->cfg.n_agents; ++a) {
+    if (h->enc_nq[a] < 1) return fail(RMX_E_INVALID, "the learner needs enc_nq (the state encoder strides) at rmx_create");
+    m = std::max(m, h->enc_nq[a]);
+  }
+  *s_max = (int64_t)h->cfg.width * h->cfg.height * m;
+  return RMX_OK;
+}
+
+int rmx_learn_bind(rmx_handle* h, const rmx_learn_config* lc, double* q, double* visits) {
+  if (!h || !lc) return fail(RMX_E_INVALID, "handle or learn config is NULL");
+  if (!q) return fail(RMX_E_INVALID, "the q table is NULL");
+  if (!std::isfinite(lc->gamma) || lc->gamma < 0.0) return fail(RMX_E_INVALID, "gamma must be finite and >= 0");
+  if (!std::isfinite(lc->learning_rate) || lc->learning_rate < 0.0)
+    return fail(RMX_E_INVALID, "learning_rate must be finite and >= 0 (0: 1 / visits)");
+  int64_t s_max = 0;
+  int rc = rmx_learn_states(h, &s_max);
+  if (rc) return rc;
+  if (lc->use_qrm && h->cfg.n_qrm_max == 0) return fail(RMX_E_INVALID, "use_qrm needs the QRM state lists (n_qrm_max == 0)");
+  if (lc->use_rsh && !lc->use_qrm)
+    return fail(RMX_E_INVALID, "use_rsh without use_qrm is not supported (the reference's non-QRM shaping reads a "
+                               "label-keyed dict by index)");
+  if (lc->use_rsh && !lc->phi) return fail(RMX_E_INVALID, "use_rsh needs phi (the RM potentials by RM index)");
+  if (lc->learning_rate == 0.0 && !visits) return fail(RMX_E_INVALID, "the 1 / visits learning rate needs a visits table");
+  if (h->cfg.stochastic || h->cfg.random_starts)
+    return fail(RMX_E_INVALID, "the learn step serves deterministic dynamics and fixed starts (cfg.stochastic / "
+                               "cfg.random_starts are set)");
+  rmx::LearnParams lp{};
+  lp.gamma = lc->gamma;
+  lp.lr = lc->learning_rate;
+  lp.q = q;
+  lp.visits = visits;
+  lp.s_max = s_max;
+  lp.use_qrm = lc->use_qrm ? 1 : 0;
+  lp.use_rsh = lc->use_rsh ? 1 : 0;
+  lp.trunc_is_terminal = lc->trunc_is_terminal ? 1 : 0;
+  const size_t n_phi = (size_t)h->cfg.n_agents * (size_t)h->cfg.n_rm_states;
+  if (h->host) {
+    try {
+      h->host->learn_phi.assign(lc->use_rsh ? lc->phi : nullptr, lc->use_rsh ? lc->phi + n_phi : nullptr);
+    } catch (const std::exception& e) {
+      return fail(RMX_E_INVALID, std::string("rmx_learn_bind: ") + e.what());
+    }
+    lp.phi = lc->use_rsh ? h->host->learn_phi.data() : nullptr;
+    h->host->learn = lp;
+    h->host->learn_on = true;
+    return RMX_OK;
+  }
+  if ((reinterpret_cast<uintptr_t>(q) & 15u) || (reinterpret_cast<uintptr_t>(visits) & 15u))
+    return fail(RMX_E_INVALID, "the q and visits tables must be 16-byte aligned");
+  SYNC_END_OR_RETURN(h);
+  HIP_TRY(hipSetDevice(h->device), "hipSetDevice");
+  if (lc->use_rsh) {
+    if (!h->d_phi) HIP_TRY(hipMalloc(&h->d_phi, sizeof(double) * n_phi), "phi alloc");
+    HIP_TRY(hipMemcpy(h->d_phi, lc->phi, sizeof(double) * n_phi, hipMemcpyHostToDevice), "phi upload");
+    lp.phi = h->d_phi;
+  }
+  h->learn = lp;
+  h->learn_on = true;
+  return RMX_OK;
+}
+
+static int do_learn_step(rmx_handle* h, const int32_t* actions, const rmx::LearnCall& lc, uint64_t seed,
+                         int64_t t_global, int autoreset, void* stream) {
+  if (!h) return fail(RMX_E_INVALID, "handle is NULL");
+  if (!h->bound) return fail(RMX_E_STATE, "buffers not bound (rmx_bind)");
+  if (!(h->host ? h->host->learn_on : h->learn_on)) return fail(RMX_E_STATE, "no learner bound (rmx_learn_bind)");
+  if (!lc.policy && !actions) return fail(RMX_E_INVALID, "actions is NULL");
+  if (h->host) {
+    h->host->step(actions, autoreset, false, seed, t_global, nullptr, &lc);
+    return RMX_OK;
+  }
+  SYNC_END_OR_RETURN(h);
+  HIP_TRY(hipSetDevice(h->device), "hipSetDevice");
+  rmx::KParams p = base_params(h);
+  p.actions = actions;
+  p.seed = seed;
+  p.t_global = t_global;
+  p.autoreset = autoreset ? 1 : 0;
+  HIP_TRY(rmx::launch_learn_step(p, h->learn, lc, h->cfg.kind, h->tables_bytes, as_stream(stream)), "learn step launch");
+  return RMX_OK;
+}
+
+int rmx_learn_step(rmx_handle* h, const int32_t* actions, int autoreset, void* stream) {
+  rmx::LearnCall lc{};
+  lc.update = 1;
+  return do_learn_step(h, actions, lc, 0, 0, autoreset, stream);
+}
+
+int rmx_learn_step_policy(rmx_handle* h, double epsilon, int flags, uint64_t seed, int64_t t_global, int autoreset,
+                          int32_t* actions_out, void* stream) {
+  if (!h) return fail(RMX_E_INVALID, "handle is NULL");
+  if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(RMX_E_INVALID, "epsilon must be in [0, 1]");
+  if (flags & ~(RMX_LEARN_UPDATE | RMX_LEARN_BEST)) return fail(RMX_E_INVALID, "unknown learn step flags");
+  rmx::LearnCall lc{};
+  lc.epsilon = epsilon;
+  lc.policy = 1;
+  lc.update = (flags & RMX_LEARN_UPDATE) ? 1 : 0;
+  lc.best = (flags & RMX_LEARN_BEST) ? 1 : 0;
+  lc.actions_out = actions_out;
+  return do_learn_step(h, nullptr, lc, seed, t_global, autoreset, stream);
 }
 
 // The fused report runs where the handle's step is the thread-per-env fast kernel with 64-thread blocks,

@@ -324,7 +324,7 @@ void HostEngine::reset(const uint8_t* mask, uint64_t seed) {
 }
 
 uint32_t HostEngine::step(const int32_t* actions, int autoreset, bool hashed, uint64_t seed, int64_t t_global,
-                          float* trace) {
+                          float* trace, const LearnCall* lc) {
   const int64_t N = cfg.n_envs;
   const int A = cfg.n_agents;
   const bool rng_on = cfg.stochastic || cfg.random_starts;
@@ -342,7 +342,9 @@ uint32_t HostEngine::step(const int32_t* actions, int autoreset, bool hashed, ui
       if ((uint32_t)s[a].x >= (uint32_t)cfg.width) s[a].x = 0;
       if ((uint32_t)s[a].y >= (uint32_t)cfg.height) s[a].y = 0;
       if ((uint32_t)s[a].q >= (uint32_t)cfg.n_rm_states) s[a].q = 0;
-      act[a] = hashed ? hash_action(seed, t_global, cfg.n_envs_global, cfg.env_offset + e, A, a) : actions[k];
+      act[a] = hashed ? hash_action(seed, t_global, cfg.n_envs_global, cfg.env_offset + e, A, a)
+               : actions   ? actions[k]
+                           : 0;
     }
     HostPcg rng = {0, 0, 0, 0};
     if (rng_on) rng = {buf.rng[e], buf.rng[N + e], buf.rng[2 * N + e], buf.rng[3 * N + e]};
@@ -354,6 +356,20 @@ uint32_t HostEngine::step(const int32_t* actions, int autoreset, bool hashed, ui
         rng = seed_pcg64(base_seed * cfg.seed_scale + (uint64_t)(cfg.env_offset + e) * cfg.seed_env_stride +
                          (uint64_t)k * cfg.seed_episode_stride);
         if (cfg.random_starts) random_starts(rng, s);  // before any slip draw of the episode
+      }
+    }
+    int32_t q_pre[RMX_MAX_AGENTS];
+    for (int a = 0; a < A; ++a) {
+      q_pre[a] = s[a].q;
+      if (lc && lc->policy) {  // the engine's policy over the row of the state the step is about to leave
+        static const double none[4] = {0.0, 0.0, 0.0, 0.0};  // a state outside the agent's table (as on the device)
+        const int64_t st = ((int64_t)s[a].y * cfg.width + s[a].x) * enc_nq[a] + s[a].q;
+        const double* row = (uint64_t)st < (uint64_t)((int64_t)cfg.width * cfg.height * enc_nq[a])
+                                ? learn.q + (((int64_t)a * N + e) * learn.s_max + st) * 4
+                                : none;
+        act[a] = learn_policy(seed, t_global, cfg.n_envs_global, cfg.env_offset + e, A, a, lc->epsilon, lc->best, row[0],
+                              row[1], row[2], row[3]);
+        if (lc->actions_out) lc->actions_out[(int64_t)a * N + e] = act[a];
       }
     }
     const float d = cfg.gamma == 1.0f ? 1.0f : disc[(size_t)std::min<uint32_t>((uint32_t)t, (uint32_t)cfg.max_t + 1u)];
@@ -413,6 +429,25 @@ uint32_t HostEngine::step(const int32_t* actions, int autoreset, bool hashed, ui
           buf.qrm_rq[off] = 0.0f;
           buf.qrm_done[off] = 0;
         }
+      }
+      // the learner's update: every agent, frozen ones included; an action without a table column (wait, or an
+      // invalid one, reported above) has nothing to update
+      if (lc && lc->update && (uint32_t)act[a] < 4u) {
+        const size_t ta = (size_t)a * cfg.n_rm_states * cfg.n_events;
+        const LearnTables T = {nq + ta,
+                               rr + ta,
+                               qrm + (size_t)a * cfg.n_qrm_max,
+                               learn.phi ? learn.phi + (size_t)a * cfg.n_rm_states : nullptr,
+                               cfg.n_events,
+                               n_qrm[a],
+                               enc_nq[a],
+                               final_q[a],
+                               cfg.reward_modifier};
+        const LearnStep st = {o[a].prev_cell, o[a].cell, o[a].ev,   q_pre[a],  s[a].q,
+                              o[a].env_term,  o[a].term, o[a].trunc, o[a].renv};
+        const int64_t base = ((int64_t)a * N + e) * learn.s_max * 4;
+        learn_agent(learn, T, st, learn.q + base, learn.visits ? learn.visits + base : nullptr, act[a],
+                    (int64_t)cfg.width * cfg.height * enc_nq[a]);
       }
     }
   }

@@ -12,6 +12,7 @@
 
 #include "../../include/rmx.h"
 #include "rmx_host.h"
+#include "rmx_learn.h"
 
 namespace rmx {
 
@@ -67,6 +68,10 @@ struct HostEngine {
   bool pending = false;   // rmx_step_sync_begin ran a step whose outputs rmx_sync_wait has not returned
   uint32_t pending_bad = 0;
   bool last_reset = false;  // the synchronous call before the copy was a reset (no step outputs)
+  // the learner bound by rmx_learn_bind (rmx_learn.h): caller tables, the engine's copy of phi
+  LearnParams learn{};
+  bool learn_on = false;
+  std::vector<double> learn_phi;
 
   // "" or the reason the config cannot run on the host path (after validate_config)
   std::string init(const rmx_config& c);
@@ -75,8 +80,10 @@ struct HostEngine {
   void reset(const uint8_t* mask, uint64_t seed);
   // rmx_step / rmx_step_hashed for every env: actions [A][N] host ints, or hashed (seed, t_global); returns 1 if an
   // action outside [0, 4] (or "wait" under FrozenLake slip) was stepped (as wait)
+  // lc != NULL: a learn step (rmx_learn_step / rmx_learn_step_policy): the policy's actions when lc->policy (seed,
+  // t_global are then the policy hash's), the bound learner's update when lc->update
   uint32_t step(const int32_t* actions, int autoreset, bool hashed = false, uint64_t seed = 0, int64_t t_global = 0,
-                float* trace = nullptr);
+                float* trace = nullptr, const LearnCall* lc = nullptr);
   void fill_actions(uint64_t seed, int64_t t0, int32_t T, int32_t* out) const;
   int64_t mdp_states(int agent) const;
   void mdp(int agent, int fix_fl, int32_t* next, float* reward, uint8_t* done) const;

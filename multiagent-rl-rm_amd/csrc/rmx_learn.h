@@ -1,0 +1,215 @@
+// rmx_learn.h — the tabular Q-learning / QRM learner's arithmetic and policy, one source for the gfx950 kernel
+// (rmx_learn.hip) and the host path (rmx_hoststep.cpp).  Plain C++: hipcc compiles it for both sides, g++ for the
+// sanitizer build.
+//
+// Reference semantics restated (paths relative to Alee08/multiagent-rl-rm):
+//   update_q          learning_algorithms/qlearning.py:70-79 (visits += 1 first; lr fixed or 1 / visits;
+//                     max_future_q = 0 when terminated; new = (1 - lr) * cur + lr * (r + gamma * max_future_q))
+//   QRM experiences   qlearning.py:82-106 over rm_environment_wrapper.py:140-183 (one update_q per state of
+//                     get_all_states()[:-1], in order, on the same table: a later one reads what an earlier one wrote)
+//   shaping           qlearning.py:93-105 (r += gamma * Phi(next) - Phi(prev), the learner's gamma)
+//   greedy ties       qlearning.py:137-143 (the maxima by equality with the row maximum, in index order), best:
+//                     np.argmax (qlearning.py:116-117)
+// Every operation below is one IEEE float64 operation, in the reference's order: contraction into fused
+// multiply-adds is off for this file's arithmetic on both sides (hipcc contracts across statements by default).
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define RMX_LEARN_HD __host__ __device__ __forceinline__
+#else
+#define RMX_LEARN_HD inline
+#endif
+#if defined(__clang__)
+#define RMX_LEARN_NOFMA _Pragma("clang fp contract(off)")
+#define RMX_LEARN_NOFMA_ATTR
+#else
+#define RMX_LEARN_NOFMA
+#define RMX_LEARN_NOFMA_ATTR __attribute__((optimize("fp-contract=off")))
+#endif
+
+namespace rmx {
+
+// The learner bound to a handle (rmx_learn_bind): caller-owned tables q / visits [A][N][S_max][4] float64, phi [A][Q]
+// (the handle's copy; NULL without use_rsh).
+struct LearnParams {
+  double gamma, lr;  // lr == 0: 1 / visits
+  double* q;
+  double* visits;
+  const double* phi;
+  int64_t s_max;  // W * H * max_a enc_nq[a]
+  int32_t use_qrm, use_rsh, trunc_is_terminal;
+};
+
+// Per-call arguments of a learn step.
+struct LearnCall {
+  double epsilon;
+  int32_t policy;  // 0: the caller's actions; 1: the engine's policy (below)
+  int32_t update;  // RMX_LEARN_UPDATE
+  int32_t best;    // RMX_LEARN_BEST
+  int32_t* actions_out;  // [A][N] or NULL (policy steps)
+};
+
+constexpr uint64_t kLearnGolden = 0x9E3779B97F4A7C15ull;
+
+RMX_LEARN_HD uint64_t learn_splitmix64(uint64_t x) {
+  uint64_t z = x + kLearnGolden;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// update_q's arithmetic: a = (1 - lr) * cur; b = gamma * maxq; c = r + b; d = lr * c; new = a + d
+RMX_LEARN_NOFMA_ATTR RMX_LEARN_HD double learn_new_q(double cur, double r, double maxq, double gamma, double lr) {
+  RMX_LEARN_NOFMA
+  const double a = (1.0 - lr) * cur;
+  const double b = gamma * maxq;
+  const double c = r + b;
+  const double d = lr * c;
+  return a + d;
+}
+
+// 1 / visits, correctly rounded
+RMX_LEARN_NOFMA_ATTR RMX_LEARN_HD double learn_rate_of(double visits) {
+  RMX_LEARN_NOFMA
+  return 1.0 / visits;
+}
+
+// r + (gamma * Phi(next) - Phi(prev))
+RMX_LEARN_NOFMA_ATTR RMX_LEARN_HD double learn_shaped(double r, double gamma, double phi_next, double phi_prev) {
+  RMX_LEARN_NOFMA
+  const double g = gamma * phi_next;
+  const double sh = g - phi_prev;
+  return r + sh;
+}
+
+// Renv + reward_modifier * RQ of the wrapper's reward (rm_environment_wrapper.py:69, 92) in float64
+RMX_LEARN_NOFMA_ATTR RMX_LEARN_HD double learn_reward(float renv, float modifier, float rq) {
+  RMX_LEARN_NOFMA
+  const double m = (double)modifier * (double)rq;
+  return (double)renv + m;
+}
+
+RMX_LEARN_HD double learn_max4(double a, double b, double c, double d) {  // np.max of a row
+  double m = a;
+  m = b > m ? b : m;
+  m = c > m ? c : m;
+  m = d > m ? d : m;
+  return m;
+}
+
+// The engine's policy for agent i of global env eg at global step t (include/rmx.h, rmx_learn_step_policy), over the
+// row of the state the step is about to leave.
+RMX_LEARN_HD int32_t learn_policy(uint64_t seed, int64_t t, int64_t n_global, int64_t eg, int A, int i, double epsilon,
+                                  int best, double r0, double r1, double r2, double r3) {
+  const double m = learn_max4(r0, r1, r2, r3);
+  if (best) return r0 == m ? 0 : r1 == m ? 1 : r2 == m ? 2 : 3;  // np.argmax: the first maximum
+  const uint64_t ctr = (((uint64_t)t * (uint64_t)n_global + (uint64_t)eg) * (uint64_t)A + (uint64_t)i) * kLearnGolden;
+  const uint64_t h0 = learn_splitmix64(seed ^ ctr);
+  const uint64_t h1 = learn_splitmix64(h0);
+  if ((double)(h1 >> 11) * 0x1p-53 < epsilon) return (int32_t)(h0 >> 62);
+  const uint64_t h2 = learn_splitmix64(h1);
+  const int e0 = r0 == m, e1 = r1 == m, e2 = r2 == m, e3 = r3 == m;
+  const uint64_t n_max = (uint64_t)(e0 + e1 + e2 + e3);
+  int pick = (int)(((h2 >> 32) * n_max) >> 32);  // maximum number `pick`, in index order
+  if (e0 && pick-- == 0) return 0;
+  if (e1 && pick-- == 0) return 1;
+  if (e2 && pick-- == 0) return 2;
+  return 3;
+}
+
+// One 32-B table row: two 16-B loads on the device (the maximum is taken in registers, by whoever uses the row)
+RMX_LEARN_HD void learn_load_row(const double* row, double (&out)[4]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double2* r2 = reinterpret_cast<const double2*>(row);
+  const double2 lo = r2[0], hi = r2[1];
+  out[0] = lo.x, out[1] = lo.y, out[2] = hi.x, out[3] = hi.y;
+#else
+  out[0] = row[0], out[1] = row[1], out[2] = row[2], out[3] = row[3];
+#endif
+}
+
+// One agent-step's outcome as the learner reads it (the kernels' AgentOut / the host's HostOut, and the RM state
+// before and after the step).
+struct LearnStep {
+  uint32_t prev_cell, cell, ev;
+  int32_t q_pre, q_post;
+  bool env_term, term, trunc;
+  float renv;
+};
+
+// The RM tables of one agent as the step reads them: next_q / rm_reward rows [Q][E] and the QRM state list.
+struct LearnTables {
+  const uint8_t* nq;   // agent a's [Q][E]
+  const float* rr;     // agent a's [Q][E]
+  const uint8_t* qrm;  // agent a's [Qx]
+  const double* phi;   // agent a's [Q] or NULL
+  int32_t E, n_qrm, enc_nq, final_q;
+  float reward_modifier;
+};
+
+// Experience j of one agent-step (qlearning.py:82-108): its table rows s / sn, reward and done flag.  use_qrm: the
+// counterfactual of RM state j of get_all_states()[:-1]; else the one real transition (j == 0).  False when there is no
+// such experience, or its state falls outside the agent's S = W * H * enc_nq rows (columns a caller overwrote out of
+// range): such an experience is dropped, never written.
+struct LearnExp {
+  int64_t s, sn;
+  double r;
+  bool done;
+};
+RMX_LEARN_HD int learn_n_exp(const LearnParams& lp, const LearnTables& T) { return lp.use_qrm ? T.n_qrm : 1; }
+RMX_LEARN_HD bool learn_experience(const LearnParams& lp, const LearnTables& T, const LearnStep& o, int j, int64_t S,
+                                   LearnExp& x) {
+  const int32_t nQ = T.enc_nq;
+  if (lp.use_qrm) {
+    if (j >= T.n_qrm) return false;
+    const uint32_t qj = T.qrm[j];
+    const uint32_t tj = qj * (uint32_t)T.E + o.ev;
+    const int32_t nqj = T.nq[tj];
+    x.s = (int64_t)o.prev_cell * nQ + (int64_t)qj;
+    x.sn = (int64_t)o.cell * nQ + nqj;
+    x.r = learn_reward(o.renv, 1.0f, T.rr[tj]);  // the raw RM reward (rm_environment_wrapper.py:171)
+    if (lp.use_rsh) x.r = learn_shaped(x.r, lp.gamma, T.phi[nqj], T.phi[qj]);
+    x.done = o.env_term || nqj == T.final_q;
+  } else {
+    if (j != 0) return false;
+    x.s = (int64_t)o.prev_cell * nQ + o.q_pre;
+    x.sn = (int64_t)o.cell * nQ + o.q_post;
+    x.r = learn_reward(o.renv, T.reward_modifier, T.rr[(uint32_t)o.q_pre * (uint32_t)T.E + o.ev]);
+    x.done = o.term || (lp.trunc_is_terminal && o.trunc);
+  }
+  return (uint64_t)x.s < (uint64_t)S && (uint64_t)x.sn < (uint64_t)S;
+}
+
+// update_q (qlearning.py:70-79) of one experience on learner table qa / va ([S_max][4], one (agent, env)): three
+// independent loads (the entry, its visit count, the next state's row unless done), then the two stores
+RMX_LEARN_HD void learn_update_q(const LearnParams& lp, double* qa, double* va, const LearnExp& x, int k) {
+  const int64_t i = x.s * 4 + k;
+  const double cur = qa[i];
+  double lr = lp.lr;
+  if (va) {
+    const double v = va[i] + 1.0;
+    va[i] = v;
+    if (lr == 0.0) lr = learn_rate_of(v);
+  }
+  double maxq = 0.0;
+  if (!x.done) {
+    double row[4];
+    learn_load_row(qa + x.sn * 4, row);
+    maxq = learn_max4(row[0], row[1], row[2], row[3]);  // np.max of the row
+  }
+  qa[i] = learn_new_q(cur, x.r, maxq, lp.gamma, lr);
+}
+
+// Every experience of one agent-step, strictly in order on the one table.  k: the action's table column (0..3).
+RMX_LEARN_HD void learn_agent(const LearnParams& lp, const LearnTables& T, const LearnStep& o, double* qa, double* va,
+                              int k, int64_t S) {
+  const int n = learn_n_exp(lp, T);
+  for (int j = 0; j < n; ++j) {
+    LearnExp x;
+    if (learn_experience(lp, T, o, j, S, x)) learn_update_q(lp, qa, va, x, k);
+  }
+}
+
+}  // namespace rmx

@@ -1,0 +1,164 @@
+// rmx_learn.hip — the learn step for gfx950: auto-reset, optional action choice, the wrapper step and the tabular
+// Q-learning / QRM update of every (env, agent) learner in ONE launch (include/rmx.h, rmx_learn_step*).
+//
+// One thread owns one environment, as in step_kernel (rmx_kernels.hip), and runs env_step of rmx_generic.h over its A
+// agents in registers: the step rules stay in one place, and the env-level rule (episode end) needs no cross-lane
+// work.  The thread then walks its agents' experiences, one agent after the other (learn_agent, rmx_learn.h): the
+// counterfactuals are formed from AgentOut and the LDS-staged RM tables and consumed on the spot; they are never
+// routed through the QRM columns.  The experiences of one agent are a dependent chain by definition (experience j may
+// read the row that j' < j wrote); each is three independent accesses (the 32-B next-state row as two 16-B loads, the
+// entry, the visit count) and two 8-B stores.  The step is bound by these sub-line accesses to HBM, not by the chain:
+// having experience j of every agent in flight together was measured and was no faster.
+// Tables are float64 [A][N][S_max][4]; every index is int64.
+//
+// Reference semantics: rmx_learn.h (update, experiences, policy), rmx_kernels.hip (the step).
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "rmx_device.h"
+#include "rmx_generic.h"
+#include "rmx_internal.h"
+#include "rmx_learn.h"
+
+namespace rmx {
+
+template <int KIND, int AMAX, bool POLICY>
+__global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams lp, LearnCall lc) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  const int64_t N = p.N;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = e < N;
+
+  AgentReg s[AMAX];
+  int32_t act[AMAX];
+  int32_t t = 0;
+  if (live) {
+    t = p.t[e];
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a) {
+      if (AMAX <= 4 || a < p.A) {
+        const int64_t k = (int64_t)a * N + e;
+        s[a].x = p.pos_x[k];
+        s[a].y = p.pos_y[k];
+        s[a].q = p.rm_q[k];
+        s[a].f = p.flags[k];
+        s[a].ret = p.ep_ret[k];
+        if constexpr (!POLICY) act[a] = p.actions[k];
+      }
+    }
+  }
+  const SlabSlot slot = slab_prefetch(p.slab);
+  stage_tables(lds, p.tables, p.tables_n16);
+  __syncthreads();
+  const Lds L = lds_view(lds, p);
+
+  LaneStats ls = {0.0, 0, 0, 0};
+  bool done = false;
+  uint32_t bad = 0;
+  AgentOut o[AMAX];
+  if (live) {
+    if (p.autoreset && (s[0].f & RMX_F_ENV_DONE)) reset_regs<AMAX>(s, t, p);
+    // the RM state the step is about to leave; the policy reads that state's row
+    int32_t q_pre[AMAX];
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a) {
+      if (AMAX <= 4 || a < p.A) {
+        q_pre[a] = s[a].q;
+        if constexpr (POLICY) {
+          const int64_t S = (int64_t)p.HW * p.enc_nq[a];
+          const int64_t st = ((int64_t)s[a].y * p.W + s[a].x) * p.enc_nq[a] + s[a].q;
+          double2 lo = make_double2(0.0, 0.0), hi = lo;
+          if ((uint64_t)st < (uint64_t)S) {
+            const double2* row = reinterpret_cast<const double2*>(lp.q + (((int64_t)a * N + e) * lp.s_max + st) * 4);
+            lo = row[0];
+            hi = row[1];
+          }
+          act[a] = learn_policy(p.seed, p.t_global, p.n_global, p.env_offset + e, p.A, a, lc.epsilon, lc.best, lo.x,
+                                lo.y, hi.x, hi.y);
+          if (lc.actions_out) lc.actions_out[(int64_t)a * N + e] = act[a];
+        }
+      }
+    }
+    const float disc = p.gamma_is_one ? 1.0f : p.disc[min((uint32_t)t, (uint32_t)p.max_t + 1u)];
+    done = env_step<KIND, AMAX>(s, t, act, L, p, disc, o, ls, &bad, nullptr);
+    p.t[e] = t;
+    if (p.env_done) p.env_done[e] = (uint8_t)done;
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a) {
+      if (AMAX <= 4 || a < p.A) {
+        const int64_t k = (int64_t)a * N + e;
+        p.pos_x[k] = s[a].x;
+        p.pos_y[k] = s[a].y;
+        p.rm_q[k] = s[a].q;
+        p.flags[k] = s[a].f;
+        p.ep_ret[k] = s[a].ret;
+        p.reward[k] = o[a].reward;
+        if (p.shaping) p.shaping[k] = o[a].shaping;
+        if (p.renv) p.renv[k] = o[a].renv;
+        if (p.enc_state) p.enc_state[k] = (s[a].y * p.W + s[a].x) * p.enc_nq[a] + s[a].q;
+        if (p.qrm_s) emit_qrm(o[a], a, e, L, p);
+      }
+    }
+    // the update: every agent, frozen ones included; an action without a table column (wait, or an invalid one,
+    // which the step has reported) has nothing to update
+    if (lc.update) {
+#pragma unroll
+      for (int a = 0; a < AMAX; ++a) {
+        if ((AMAX <= 4 || a < p.A) && (uint32_t)act[a] < 4u) {
+          LearnTables T;
+          T.nq = L.nq + a * p.Q * p.E;
+          T.rr = L.rr + a * p.Q * p.E;
+          T.qrm = L.qrm + a * p.n_qrm_max;
+          T.phi = lp.phi ? lp.phi + a * p.Q : nullptr;
+          T.E = p.E;
+          T.n_qrm = p.n_qrm[a];
+          T.enc_nq = p.enc_nq[a];
+          T.final_q = p.final_q[a];
+          T.reward_modifier = p.reward_modifier;
+          const LearnStep st = {o[a].prev_cell, o[a].cell, o[a].ev,     q_pre[a],
+                                s[a].q,         o[a].env_term, o[a].term, o[a].trunc, o[a].renv};
+          const int64_t base = ((int64_t)a * N + e) * lp.s_max * 4;
+          learn_agent(lp, T, st, lp.q + base, lp.visits ? lp.visits + base : nullptr, act[a],
+                      (int64_t)p.HW * p.enc_nq[a]);
+        }
+      }
+    }
+  }
+  if (__any(bad)) {
+    if ((threadIdx.x & 63) == 0) atomicOr(p.err, 1u);
+  }
+  wave_flush_slot(p.slab, slot, ls, __any(done));
+}
+
+template <int KIND, int AMAX>
+static hipError_t launch_learn_t(const KParams& p, const LearnParams& lp, const LearnCall& lc, dim3 g, dim3 b,
+                                 size_t lds, hipStream_t st) {
+  if (lc.policy)
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, true>), g, b, lds, st, p, lp, lc);
+  else
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, false>), g, b, lds, st, p, lp, lc);
+  return hipGetLastError();
+}
+
+template <int KIND>
+static hipError_t launch_learn_k(const KParams& p, const LearnParams& lp, const LearnCall& lc, dim3 g, dim3 b,
+                                 size_t lds, hipStream_t st) {
+  switch (amax_bucket(p.A)) {
+    case 1: return launch_learn_t<KIND, 1>(p, lp, lc, g, b, lds, st);
+    case 2: return launch_learn_t<KIND, 2>(p, lp, lc, g, b, lds, st);
+    case 3: return launch_learn_t<KIND, 3>(p, lp, lc, g, b, lds, st);
+    case 4: return launch_learn_t<KIND, 4>(p, lp, lc, g, b, lds, st);
+    default: return launch_learn_t<KIND, 8>(p, lp, lc, g, b, lds, st);
+  }
+}
+
+// 256-thread blocks, one thread per env (the per-wave statistics slab is sized for that geometry at rmx_create)
+hipError_t launch_learn_step(const KParams& p, const LearnParams& lp, const LearnCall& lc, int kind, size_t lds,
+                             hipStream_t st) {
+  const dim3 g((unsigned)((p.N + 255) / 256)), b(256);
+  return kind == RMX_FROZEN_LAKE ? launch_learn_k<RMX_FROZEN_LAKE>(p, lp, lc, g, b, lds, st)
+                                 : launch_learn_k<RMX_OFFICE_WORLD>(p, lp, lc, g, b, lds, st);
+}
+
+}  // namespace rmx

@@ -28,8 +28,9 @@ EXPORTS = (
     "rmx_get_state", "rmx_set_state", "rmx_step_report", "rmx_step_report_fused", "rmx_reset_sync", "rmx_step_sync",
     "rmx_step_sync_begin", "rmx_sync_wait", "rmx_sync_end", "rmx_step_seq", "rmx_queue_counters", "rmx_queue_info",
     "rmx_code_object_check", "rmx_device_count", "rmx_queue_timing", "rmx_queue_times", "rmx_step_info",
-    "rmx_seq_packed",
+    "rmx_seq_packed", "rmx_learn_states", "rmx_learn_bind", "rmx_learn_step", "rmx_learn_step_policy",
 )
+LEARN_UPDATE, LEARN_BEST = 1, 2  # RMX_LEARN_*
 SYNC_MAX_ENVS = 256  # RMX_SYNC_MAX_ENVS
 QUEUE_INFO_N = 7  # RMX_QUEUE_INFO_N
 QUEUE_STATES = ("unused", "ready", "unavailable", "retired")  # RMX_QUEUE_*
@@ -52,7 +53,8 @@ ABI_VERSION = 12  # include/rmx.h RMX_ABI_VERSION
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
 HASHED_SOURCES = ("rmx_kernels.hip", "rmx_fast.hip", "rmx_fast_step.inc", "rmx_sync.hip", "rmx_capi.cpp",
                   "rmx_queue.cpp", "rmx_tables.cpp", "rmx_comd.cpp", "rmx_build_info.cpp", "rmx_internal.h", "rmx_layout.h", "rmx_host.h", "rmx_device.h",
-                  "rmx_generic.h", "rmx_comd.h", "rmx_hoststep.cpp", "rmx_hoststep.h", "../../include/rmx.h",
+                  "rmx_generic.h", "rmx_comd.h", "rmx_hoststep.cpp", "rmx_hoststep.h", "rmx_learn.hip", "rmx_learn.h",
+                  "../../include/rmx.h",
                   "Makefile")
 
 
@@ -88,6 +90,11 @@ class RmxConfig(C.Structure):
         ("shape", C.c_void_p), ("init_q", C.c_void_p), ("final_q", C.c_void_p), ("start_xy", C.c_void_p),
         ("n_qrm", C.c_void_p), ("qrm_states", C.c_void_p), ("enc_nq", C.c_void_p),
     ]
+
+
+class RmxLearnConfig(C.Structure):
+    _fields_ = [("gamma", C.c_double), ("learning_rate", C.c_double), ("use_qrm", C.c_int32), ("use_rsh", C.c_int32),
+                ("trunc_is_terminal", C.c_int32), ("reserved", C.c_int32), ("phi", C.c_void_p)]
 
 
 class RmxBuffers(C.Structure):
@@ -220,6 +227,10 @@ def load_library(path: str = None, check_source: bool = True):
         "rmx_step_sync_begin": (C.c_int, [vp, vp, C.c_int, vp]),
         "rmx_sync_wait": (C.c_int, [vp, C.POINTER(RmxBuffers)]),
         "rmx_sync_end": (C.c_int, [vp]),
+        "rmx_learn_states": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "rmx_learn_bind": (C.c_int, [vp, C.POINTER(RmxLearnConfig), vp, vp]),
+        "rmx_learn_step": (C.c_int, [vp, vp, C.c_int, vp]),
+        "rmx_learn_step_policy": (C.c_int, [vp, C.c_double, C.c_int, u64, i64, C.c_int, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

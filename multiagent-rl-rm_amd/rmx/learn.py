@@ -1,0 +1,121 @@
+"""``VecQLearning`` — one tabular Q-learning / QRM learner per (env, agent), updated inside the step launch.
+
+The batched equivalent of attaching the reference's ``QLearning`` (learning_algorithms/qlearning.py:6-110) to every
+agent and calling ``update_policy`` after every step as the runners do (frozen_lake_main.py:345-376,
+office_main.py:1709-1749): N replicas of the runner's experiment in one process, each learner's table bit-comparable
+with the reference's ``q_table`` (include/rmx.h, "tabular Q-learning / QRM learners").  On a ``VecRMEnv`` the tables
+are torch tensors on the engine's GPU and a learn step is one kernel launch (csrc/rmx_learn.hip); on a ``HostRMEnv``
+they are numpy arrays and the host path runs the same arithmetic (csrc/rmx_learn.h).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from .tables import FROZEN_LAKE
+
+
+class VecQLearning:
+    """``q`` and ``visits``: ``[A, N, S_max, 4]`` float64, ``q[a, e]`` the ``q_table`` of agent a's learner in env e
+    (rows past ``W*H*enc_nq[a]`` unused).  ``learning_rate=None`` is the reference's ``1 / visits`` rate.
+    ``trunc_is_terminal=None`` follows the env kind: the FrozenLake runner passes ``done or truncated`` to the update,
+    the OfficeWorld runner ``done``."""
+
+    def __init__(self, env, gamma, learning_rate=None, qtable_init=1.0, use_qrm=False, use_rsh=False,
+                 trunc_is_terminal=None):
+        # argument checks before the tables are allocated (several GB on a GPU env)
+        if learning_rate is not None and float(learning_rate) == 0.0:
+            raise ValueError("learning_rate must be > 0, or None for 1 / visits")
+        if use_rsh and not use_qrm:
+            raise ValueError("use_rsh without use_qrm is not supported (rmx_learn_bind refuses it: the reference's "
+                             "non-QRM shaping reads a label-keyed dict by index)")
+        self.env, self.lib = env, env.lib
+        self.host = getattr(env, "device", None) == "cpu"
+        tab = env.tables
+        if trunc_is_terminal is None:
+            trunc_is_terminal = tab.kind == FROZEN_LAKE
+        s_max = C.c_int64()
+        _capi.check(self.lib.rmx_learn_states(env._h, C.byref(s_max)), "rmx_learn_states")
+        self.S_max = int(s_max.value)
+        self.n_states = [tab.width * tab.height * int(n) for n in tab.enc_nq]
+        shape = (env.A, env.N, self.S_max, 4)
+        if self.host:
+            self.q = np.full(shape, float(qtable_init), np.float64)
+            self.visits = np.zeros(shape, np.float64)
+            ptr = lambda x: x.ctypes.data  # noqa: E731
+        else:
+            t = env.torch
+            self.q = t.full(shape, float(qtable_init), dtype=t.float64, device=env.device)
+            self.visits = t.zeros(shape, dtype=t.float64, device=env.device)
+            ptr = lambda x: x.data_ptr()  # noqa: E731
+        self._phi = None
+        if use_rsh and tab.phi is not None:
+            self._phi = np.ascontiguousarray(tab.phi, np.float64)
+        cfg = _capi.RmxLearnConfig()
+        cfg.gamma = float(gamma)
+        cfg.learning_rate = 0.0 if learning_rate is None else float(learning_rate)
+        cfg.use_qrm, cfg.use_rsh, cfg.trunc_is_terminal = int(bool(use_qrm)), int(bool(use_rsh)), int(bool(trunc_is_terminal))
+        cfg.phi = None if self._phi is None else self._phi.ctypes.data
+        _capi.check(self.lib.rmx_learn_bind(env._h, C.byref(cfg), ptr(self.q), ptr(self.visits)), "rmx_learn_bind")
+        self.gamma, self.learning_rate = float(gamma), learning_rate
+        self.use_qrm, self.use_rsh, self.trunc_is_terminal = bool(use_qrm), bool(use_rsh), bool(trunc_is_terminal)
+
+    def _stream(self):
+        return None if self.host else self.env._stream()
+
+    def step(self, actions, autoreset=True):
+        """One wrapper step with the caller's actions ([A, N] int32, 0..3) and every learner's update."""
+        env = self.env
+        if self.host:
+            a = env._acts(actions)
+            p = a.ctypes.data
+        else:
+            t = env.torch
+            a = actions
+            if a.dtype is not t.int32 or a.get_device() != env.device.index or not a.is_contiguous():
+                a = a.to(device=env.device, dtype=t.int32).contiguous()
+            if a.numel() != env.A * env.N:
+                raise ValueError(f"actions must be [A={env.A}, N={env.N}]")
+            p = a.data_ptr()
+        _capi.check(self.lib.rmx_learn_step(env._h, p, 1 if autoreset else 0, self._stream()), "rmx_learn_step")
+
+    def act_step(self, epsilon, seed, t_global, best=False, learn=True, autoreset=True, actions_out=None):
+        """One step with the engine's policy (epsilon-greedy over each learner's own row with hash-chosen ties;
+        ``best``: np.argmax), and with ``learn`` the update.  ``actions_out``: an [A, N] int32 array / tensor that
+        receives the chosen actions."""
+        env = self.env
+        p = None
+        if actions_out is not None:
+            if self.host:
+                p = env._out(actions_out, np.int32, env.A * env.N, "actions_out").ctypes.data
+            else:
+                t = env.torch
+                if actions_out.dtype is not t.int32 or actions_out.get_device() != env.device.index or \
+                        not actions_out.is_contiguous() or actions_out.numel() < env.A * env.N:
+                    raise ValueError("actions_out must be a contiguous int32 [A, N] tensor on the engine's device")
+                p = actions_out.data_ptr()
+        flags = (_capi.LEARN_UPDATE if learn else 0) | (_capi.LEARN_BEST if best else 0)
+        _capi.check(self.lib.rmx_learn_step_policy(env._h, float(epsilon), flags, int(seed) & (2**64 - 1),
+                                                   int(t_global), 1 if autoreset else 0, p, self._stream()),
+                    "rmx_learn_step_policy")
+        return actions_out
+
+    def greedy(self):
+        """np.argmax of every learner's row at its env's current state: [A, N] (numpy int64 / torch int64)."""
+        env, tab = self.env, self.env.tables
+        env.sync_end()
+        if self.host:
+            nq = np.asarray(tab.enc_nq, np.int64)[:, None]
+            s = (env.pos_y.astype(np.int64) * tab.width + env.pos_x) * nq + env.rm_q
+            rows = np.take_along_axis(self.q, s[:, :, None, None].repeat(4, axis=3), axis=2)[:, :, 0, :]
+            return np.argmax(rows, axis=-1)
+        t = env.torch
+        nq = t.as_tensor(np.asarray(tab.enc_nq, np.int64), device=env.device)[:, None]
+        s = (env.pos_y.to(t.int64) * tab.width + env.pos_x) * nq + env.rm_q
+        rows = t.gather(self.q, 2, s[:, :, None, None].expand(-1, -1, 1, 4))[:, :, 0, :]
+        m = rows.max(dim=-1).values  # the first maximum, as np.argmax (torch.argmax leaves ties open)
+        three = t.full_like(s, 3)
+        return t.where(rows[..., 0] == m, three - 3,
+                       t.where(rows[..., 1] == m, three - 2, t.where(rows[..., 2] == m, three - 1, three)))

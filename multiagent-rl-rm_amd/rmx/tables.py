@@ -277,6 +277,8 @@ class CompiledTables:
     random_starts: int = 0
     rms: List[RewardMachineSpec] = field(default_factory=list)
     event_cells: List[Pos] = field(default_factory=list)  # event id k>=1 -> cell
+    # the RMs' potentials by RM index (qlearning.py:93-105 reads them for the shaped QRM update), with shaping only
+    phi: Optional[np.ndarray] = None         # float64 [A][Q]
 
     def label_of(self, agent: int, q_index: int):
         return self.rms[agent].get_state_from_index(int(q_index))
@@ -386,6 +388,7 @@ def compile_tables(kind: int, width: int, height: int, hazards, walls, starts: S
     next_q = np.zeros((A, Q, E), np.uint8)
     rr = np.zeros((A, Q, E), np.float64)
     shape = np.zeros((A, Q, E), np.float64) if shaping_gamma is not None else None
+    phi_all = np.zeros((A, Q), np.float64) if shaping_gamma is not None else None
     init_q = np.zeros(A, np.int32)
     final_q = np.zeros(A, np.int32)
     for a, rm in enumerate(rms):
@@ -400,6 +403,7 @@ def compile_tables(kind: int, width: int, height: int, hazards, walls, starts: S
             phi = np.array([rm.potentials.get(inv.get(q), 0) if q in inv else 0.0 for q in range(Q)], np.float64)
             # shaping = gamma * Phi(q') - Phi(q) (qlearning.py:60-65, 99-105), f64 then f32
             shape[a] = shaping_gamma * phi[next_q[a].astype(np.int64)] - phi[:, None]
+            phi_all[a] = phi
     if hazard_fail is None:
         hazard_fail = kind == FROZEN_LAKE
     qlists = [[rm.state_indices[u] for u in rm.get_all_states()[:-1]] for rm in rms]
@@ -421,7 +425,8 @@ def compile_tables(kind: int, width: int, height: int, hazards, walls, starts: S
         hazard_penalty=float(hazard_penalty), wall_penalty=float(wall_penalty), hazard_fail=int(bool(hazard_fail)),
         wall_fail=int(bool(wall_fail)), gamma=float(gamma), max_t=int(max_t), reward_modifier=float(reward_modifier),
         n_qrm=np.array([len(ql) for ql in qlists], np.int32), qrm_states=qrm_states,
-        enc_nq=np.array([rm.numbers_state() for rm in rms], np.int32), rms=list(rms), event_cells=ev_cells)
+        enc_nq=np.array([rm.numbers_state() for rm in rms], np.int32), rms=list(rms), event_cells=ev_cells,
+        phi=phi_all)
 
 
 # --------------------------------------------------------------------------------------------------
