@@ -384,7 +384,12 @@ int rmx_step_info(const rmx_handle* h, int64_t* out, int32_t n);
  *   its >> 62), h1 = splitmix64(h0), h2 = splitmix64(h1); explore iff (h1 >> 11) * 2^-53 < epsilon, with action
  *   h0 >> 62; else greedy: the row's maxima by float64 equality with the row maximum, in index order, maximum number
  *   ((h2 >> 32) * n_max) >> 32 (qlearning.py:137-143 with the engine's draw).  RMX_LEARN_BEST: the first maximum
- *   (np.argmax, qlearning.py:116-117).
+ *   (np.argmax, qlearning.py:116-117).  The row maximum is m = row[0], then m = v for every later v > m: a NaN in
+ *   row[0] stays, a NaN further on is skipped.  A row with no entry equal to its maximum (a NaN maximum) gives
+ *   action 3, greedy and RMX_LEARN_BEST alike (the explore draw comes first and does not look at the row).
+ *   A state outside the agent's W*H*enc_nq[a] rows (pos_x / pos_y / rm_q columns the caller overwrote out of range)
+ *   reads a row of four zeros, never table memory; an experience whose s or sn is outside those rows is dropped:
+ *   neither q nor visits is written (with use_rsh also when nq_j is no RM index, before phi is read).
  * Each learn step is ONE launch on the caller's stream: auto-reset, action choice, step, update.  It leaves every
  * bound column (enc_state and the QRM columns included) and the episode statistics as rmx_step with the same actions
  * leaves them (the statistics through the generic kernels' per-wave slots: the integer ones equal, the return sum in

@@ -442,7 +442,8 @@ uint32_t HostEngine::step(const int32_t* actions, int autoreset, bool hashed, ui
                                n_qrm[a],
                                enc_nq[a],
                                final_q[a],
-                               cfg.reward_modifier};
+                               cfg.reward_modifier,
+                               cfg.n_rm_states};
         const LearnStep st = {o[a].prev_cell, o[a].cell, o[a].ev,   q_pre[a],  s[a].q,
                               o[a].env_term,  o[a].term, o[a].trunc, o[a].renv};
         const int64_t base = ((int64_t)a * N + e) * learn.s_max * 4;

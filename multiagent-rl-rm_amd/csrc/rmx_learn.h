@@ -147,12 +147,14 @@ struct LearnTables {
   const double* phi;   // agent a's [Q] or NULL
   int32_t E, n_qrm, enc_nq, final_q;
   float reward_modifier;
+  int32_t Q;  // cfg.n_rm_states: the length of phi's row
 };
 
 // Experience j of one agent-step (qlearning.py:82-108): its table rows s / sn, reward and done flag.  use_qrm: the
 // counterfactual of RM state j of get_all_states()[:-1]; else the one real transition (j == 0).  False when there is no
 // such experience, or its state falls outside the agent's S = W * H * enc_nq rows (columns a caller overwrote out of
-// range): such an experience is dropped, never written.
+// range): such an experience is dropped, never written.  In such a state the kernel's event and successor come from
+// table bytes outside the agent's own, so nq_j can be any byte: it is checked before it indexes phi (global memory).
 struct LearnExp {
   int64_t s, sn;
   double r;
@@ -170,7 +172,10 @@ RMX_LEARN_HD bool learn_experience(const LearnParams& lp, const LearnTables& T, 
     x.s = (int64_t)o.prev_cell * nQ + (int64_t)qj;
     x.sn = (int64_t)o.cell * nQ + nqj;
     x.r = learn_reward(o.renv, 1.0f, T.rr[tj]);  // the raw RM reward (rm_environment_wrapper.py:171)
-    if (lp.use_rsh) x.r = learn_shaped(x.r, lp.gamma, T.phi[nqj], T.phi[qj]);
+    if (lp.use_rsh) {
+      if ((uint32_t)nqj >= (uint32_t)T.Q) return false;
+      x.r = learn_shaped(x.r, lp.gamma, T.phi[nqj], T.phi[qj]);
+    }
     x.done = o.env_term || nqj == T.final_q;
   } else {
     if (j != 0) return false;

@@ -116,6 +116,7 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
           T.enc_nq = p.enc_nq[a];
           T.final_q = p.final_q[a];
           T.reward_modifier = p.reward_modifier;
+          T.Q = p.Q;
           const LearnStep st = {o[a].prev_cell, o[a].cell, o[a].ev,     q_pre[a],
                                 s[a].q,         o[a].env_term, o[a].term, o[a].trunc, o[a].renv};
           const int64_t base = ((int64_t)a * N + e) * lp.s_max * 4;

@@ -46,6 +46,13 @@ FL_BACK = [["s0", "A", "s1", 1], ["s1", "B", "s0", 0.5], ["s1", "A", "s2", 2]]
 G.CONFIGS["fl2_back"] = {"kind": "frozen_lake", "layout": G.OPEN_LAKE, "penalty": 0.0,
                          "agents": [{"start": [4, 4], "rm": FL_BACK}, {"start": [3, 1], "rm": G.FL_AB}]}
 CASES["fl2_back_qrm"] = ("fl2_back", 2, 1100, 37, dict(gamma=0.9, lr=0.3, use_qrm=True, use_rsh=False))
+# 200 counterfactual updates per step (the 201-state chain of the limit goldens on the two-cell lake): QRM list entries
+# and table rows with RM index >= 128, 402-row learners.  The hashed walk itself climbs the chain slowly: measured on
+# the recording, the RM state after the step is >= 128 in 0.000 of the 300 x 2 (step, env) samples (0 of 600, highest
+# state 77).  The rows with RM index >= 128 are visited all the same, in every snapshot, by the counterfactual updates
+# (asserted in run()): they are what a narrow q_j or row index would corrupt.
+CASES["fl1_chain200_qrm"] = ("fl1_chain200", 2, 300, 38, dict(gamma=0.95, lr=0.3, use_qrm=True, use_rsh=False))
+HIGH_Q_SHARE = {"fl1_chain200_qrm": None}  # filled by run(): the measured share
 QINIT = 1.0
 
 
@@ -66,7 +73,7 @@ def run(case):
     q = np.full((3, A, N, S_max, 4), QINIT, np.float64)
     visits = np.zeros((3, A, N, S_max, 4), np.float64)
     acts = np.zeros((T, A, N), np.int8)
-    n_done = n_alias = n_trunc = 0
+    n_done = n_alias = n_trunc = n_high = q_top = 0
     for v in (cfg.get("penalty", 0.0), cfg.get("plants_penalty", 0.0), cfg.get("wall_penalty", 0.0),
               cfg.get("reward_modifier", 1.0)):
         assert f32(v), f"{case}: {v} is not a float32 value"
@@ -107,6 +114,9 @@ def run(case):
                 ag.update_policy(state=states[ag.name], action=actions[ag.name], reward=rewards[ag.name],
                                  next_state=new_states[ag.name], terminated=terminated, infos=infos[ag.name])
             states = copy.deepcopy(new_states)
+            q_now = [ag.get_reward_machine().get_state_index(ag.get_reward_machine().get_current_state()) for ag in agents]
+            n_high += sum(v >= 128 for v in q_now)
+            q_top = max([q_top] + q_now)
             if all(terms.values()) or all(truncs.values()):
                 need_reset = True
                 episode += 1
@@ -130,6 +140,12 @@ def run(case):
         assert n_trunc >= 1, case
     if case == "fl2_visits":
         assert n_trunc == 0, (case, n_trunc)
+    if case in HIGH_Q_SHARE:  # RM indices above 127 are lived in, and their rows are in every snapshot
+        nQ = S[0] // (W * H)
+        high = (np.arange(S_max) % nQ) >= 128
+        assert all((visits[k, 0, :, high] > 0).any() for k in range(3)), case
+        HIGH_Q_SHARE[case] = n_high / (T * N * A)
+        print(f"{case}: RM state >= 128 in {HIGH_Q_SHARE[case]:.3f} of the {T} x {N} samples, highest {q_top}")
     print(f"{case}: visited share {share:.3f}, done {n_done}, same-call rows {n_alias}, truncated updates {n_trunc}")
     return dict(actions=acts, seed=np.int64(seed), config=np.array(cfg_name),
                 scenario=np.array(json.dumps(cfg)), gamma=np.float64(lp["gamma"]),

@@ -18,16 +18,30 @@ def splitmix64(x):
     return z ^ (z >> 31)
 
 
+def row_max(row):
+    """np.max of a row as the engine takes it: m = row[0], then m = v where v > m.  A NaN in row[0] stays (no
+    comparison with it is true); a NaN further on is skipped."""
+    m = float(row[0])
+    for v in row[1:]:
+        if float(v) > m:
+            m = float(v)
+    return m
+
+
 def policy_action(row, seed, t, n_global, e, A, i, epsilon, best):
-    m = max(float(v) for v in row)
+    """include/rmx.h, "the engine's policy".  A row with no entry equal to its maximum (a NaN maximum) gives action
+    3, greedy and best alike; an explore draw comes before the row is looked at."""
+    m = row_max(row)
     maxs = [k for k in range(4) if float(row[k]) == m]
     if best:
-        return maxs[0]
+        return maxs[0] if maxs else 3
     h0 = splitmix64((seed ^ ((((t * n_global + e) * A + i) * GOLDEN) & M64)) & M64)
     h1 = splitmix64(h0)
     h2 = splitmix64(h1)
     if (h1 >> 11) * 2.0 ** -53 < epsilon:
         return h0 >> 62
+    if not maxs:
+        return 3
     return maxs[((h2 >> 32) * len(maxs)) >> 32]
 
 
@@ -58,22 +72,29 @@ class LearnRef:
         nq = np.asarray(self.tab.enc_nq, np.int64)[:, None]
         return (y.astype(np.int64) * self.tab.width + x) * nq + q
 
+    def n_rows(self, a):
+        """Agent a's own rows, W * H * enc_nq[a]: a state outside them has no row (a column the caller overwrote)."""
+        return self.tab.width * self.tab.height * int(self.tab.enc_nq[a])
+
     def choose(self, epsilon, seed, t_global, best=False, autoreset=True):
         tw = self.twin
         s = self.encode(*self.pre_state(autoreset))
         out = np.zeros((self.A, self.N), np.int32)
         for a in range(self.A):
             for e in range(self.N):
-                out[a, e] = policy_action(self.q[a, e, s[a, e]], seed, t_global, tw.n_envs_global, tw.env_offset + e,
-                                          self.A, a, epsilon, best)
+                row = self.q[a, e, s[a, e]] if 0 <= s[a, e] < self.n_rows(a) else (0.0, 0.0, 0.0, 0.0)  # a zero row
+                out[a, e] = policy_action(row, seed, t_global, tw.n_envs_global, tw.env_offset + e, self.A, a,
+                                          epsilon, best)
         return out
 
     def update_q(self, a, e, s, k, r, sn, done):
+        if not (0 <= s < self.n_rows(a) and 0 <= sn < self.n_rows(a)):
+            return  # dropped, never written: the experience's state is outside the agent's rows
         q, v = self.q[a, e], self.visits[a, e]
         cur = float(q[s, k])
         v[s, k] += 1.0
         lr = 1.0 / float(v[s, k]) if self.lr is None else float(self.lr)
-        maxq = 0.0 if done else max(float(z) for z in q[sn])
+        maxq = 0.0 if done else row_max(q[sn])
         x = (1.0 - lr) * cur
         b = self.gamma * maxq
         c = r + b
@@ -106,6 +127,9 @@ class LearnRef:
                             r = r + sh
                         self.update_q(a, e, s, k, r, sn, bool(tw.qrm_done[a, j, e]))
                 else:
+                    if not (0 <= px[a, e] < tab.width and 0 <= py[a, e] < tab.height
+                            and 0 <= pq[a, e] < tab.n_rm_states):
+                        continue  # a pre-step column outside the grid / the RM tables: the engine's result is unspecified
                     cell = int(tw.pos_y[a, e]) * tab.width + int(tw.pos_x[a, e])
                     rq = float(tab.rm_reward[a, pq[a, e], tab.cell_event[a, cell]])
                     m = float(np.float32(tab.reward_modifier)) * rq
