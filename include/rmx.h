@@ -390,6 +390,38 @@ int rmx_step_info(const rmx_handle* h, int64_t* out, int32_t n);
  *   A state outside the agent's W*H*enc_nq[a] rows (pos_x / pos_y / rm_q columns the caller overwrote out of range)
  *   reads a row of four zeros, never table memory; an experience whose s or sn is outside those rows is dropped:
  *   neither q nor visits is written (with use_rsh also when nq_j is no RM index, before phi is read).
+ * The reference's policy (rmx_learn_step_policy with RMX_LEARN_NUMPY; seed and t_global are ignored): QLearning.
+ * choose_action (qlearning.py:112-143, action_selection "greedy") on each learner's own np.random.default_rng(seed)
+ * (learning_algorithm.py:32), as the runners call it through select_action for every agent every step, frozen and
+ * inactive ones included (frozen_lake_main.py:269-295 seeds every learner with 2020, office_main.py:704-717 with
+ * args.seed).  Learner (a, e) owns one PCG64 generator in the column bound by rmx_learn_rng_bind; on every such step
+ * that is not RMX_LEARN_BEST, over the same row as above:
+ *   d = (next_uint64() >> 11) * 2^-53 (Generator.uniform(0, 1)), drawn whatever epsilon is; explore iff d < epsilon,
+ *   with action bounded(4); else greedy: m the row maximum by the rule above, k the number of entries equal to m, the
+ *   action is maximum number bounded(k) in index order; k == 0 (a NaN maximum; the reference raises there) gives
+ *   action 3 and draws nothing more.
+ *   bounded(k) = Generator.choice of a k-sequence = integers(0, k), Lemire's method on buffered 32-bit draws: k == 1
+ *   returns 0 and draws nothing; else m64 = (uint64)next_uint32() * k, left = (uint32)m64; if left < k then thr =
+ *   (0xFFFFFFFF - (k-1)) % k and m64 is redrawn while left < thr; the result is m64 >> 32 (thr is 0 for k = 2 and 4:
+ *   only k = 3 can redraw, on left == 0).  next_uint32() is PCG64's buffered draw: a buffered half is returned and
+ *   the flag cleared, else 64 bits are drawn, the low half returned and the high half buffered; next_uint64() never
+ *   touches the buffer.
+ *   With RMX_LEARN_BEST as well, best wins: nothing is drawn and the column is not touched.  Without
+ *   RMX_LEARN_UPDATE the draws still happen (select_action without update_policy).
+ * Bit-exactness of a run: with epsilon fixed (the runners never call learn_done_episode, so epsilon stays at
+ * epsilon_start), deterministic dynamics and fixed starts (all the learn step serves) and float32 rewards as above,
+ * the actions of every step, q, visits and each generator's state after T steps equal those of the runner's loop
+ * (select_action for every agent, rm_env.step, update_policy for every agent) bit for bit, on the device and on the
+ * host, whatever the sharding (a learner's stream depends on its own column words only).
+ * The generator column is caller-owned like q and visits: uint64 rng[5][A][N], plane-major, word w of learner (a, e)
+ * at rng[(w*A + a)*N + e]: 0 state high, 1 state low, 2 increment high, 3 increment low (numpy's bit_generator.state
+ * "state" / "inc" as 128-bit numbers), 4 (has_uint32 << 32) | uinteger.  A learn step reads a learner's five words
+ * and writes words 0, 1 and, when it changed, 4.  A device handle takes a device pointer, a host handle a host
+ * pointer, 16-byte aligned; NULL unbinds; the extent (5 * A * N words) cannot be checked; the column is not part of
+ * rmx_get_state.  rmx_learn_rng_seed fills the bound column with default_rng(seeds[a][e]) (SeedSequence -> PCG64, any
+ * uint64 seed; nothing buffered) from host seeds [A][N], in stream order, and returns when the column is written.
+ * RMX_E_STATE: rmx_learn_rng_bind / rmx_learn_rng_seed before rmx_learn_bind, rmx_learn_rng_seed or RMX_LEARN_NUMPY
+ * with no column bound; RMX_E_INVALID: a misaligned column, NULL seeds; each with a message, before any device work.
  * Each learn step is ONE launch on the caller's stream: auto-reset, action choice, step, update.  It leaves every
  * bound column (enc_state and the QRM columns included) and the episode statistics as rmx_step with the same actions
  * leaves them (the statistics through the generic kernels' per-wave slots: the integer ones equal, the return sum in
@@ -408,6 +440,7 @@ typedef struct rmx_learn_config {
 } rmx_learn_config;
 #define RMX_LEARN_UPDATE 1
 #define RMX_LEARN_BEST 2
+#define RMX_LEARN_NUMPY 4 /* rmx_learn_step_policy: the reference's policy on the learners' own numpy generators */
 int rmx_learn_states(const rmx_handle* h, int64_t* s_max);
 int rmx_learn_bind(rmx_handle* h, const rmx_learn_config* cfg, double* q, double* visits);
 /* rmx_step with the caller's actions, then the update */
@@ -415,6 +448,9 @@ int rmx_learn_step(rmx_handle* h, const int32_t* actions, int autoreset, void* h
 /* the policy's actions (written to actions_out [A][N] unless NULL), the step, and with RMX_LEARN_UPDATE the update */
 int rmx_learn_step_policy(rmx_handle* h, double epsilon, int flags, uint64_t seed, int64_t t_global, int autoreset,
                           int32_t* actions_out, void* hip_stream);
+/* the learners' numpy generators for RMX_LEARN_NUMPY: bind the caller's column [5][A][N] (NULL unbinds), seed it */
+int rmx_learn_rng_bind(rmx_handle* h, uint64_t* rng);
+int rmx_learn_rng_seed(rmx_handle* h, const uint64_t* seeds_host /* [A][N] */, void* hip_stream);
 
 /* Synchronise and report kernel-side errors (e.g. RMX_E_ACTION), then clear them. */
 int rmx_check_errors(rmx_handle* h);

@@ -163,6 +163,7 @@ struct rmx_handle {
   rmx::LearnParams learn{};
   bool learn_on = false;
   double* d_phi = nullptr;
+  uint64_t* learn_rng = nullptr;  // rmx_learn_rng_bind: the learners' numpy generators, caller's [5][A][N]
 #ifdef RMX_DIAG
   std::chrono::steady_clock::time_point sy_t_post;  // diag: when the last request was posted
   double sy_wait_ns = 0;                             // diag: post -> acknowledgement seen by the host
@@ -1193,12 +1194,56 @@ int rmx_learn_bind(rmx_handle* h, const rmx_learn_config* lc, double* q, double*
   return RMX_OK;
 }
 
-static int do_learn_step(rmx_handle* h, const int32_t* actions, const rmx::LearnCall& lc, uint64_t seed,
-                         int64_t t_global, int autoreset, void* stream) {
+int rmx_learn_rng_bind(rmx_handle* h, uint64_t* rng) {
+  if (!h) return fail(RMX_E_INVALID, "handle is NULL");
+  if (!(h->host ? h->host->learn_on : h->learn_on))
+    return fail(RMX_E_STATE, "no learner bound (rmx_learn_bind comes before rmx_learn_rng_bind)");
+  if (reinterpret_cast<uintptr_t>(rng) & 15u) return fail(RMX_E_INVALID, "the generator column must be 16-byte aligned");
+  if (h->host)
+    h->host->learn_rng = rng;
+  else
+    h->learn_rng = rng;
+  return RMX_OK;
+}
+
+int rmx_learn_rng_seed(rmx_handle* h, const uint64_t* seeds, void* stream) {
+  if (!h) return fail(RMX_E_INVALID, "handle is NULL");
+  if (!(h->host ? h->host->learn_on : h->learn_on))
+    return fail(RMX_E_STATE, "no learner bound (rmx_learn_bind comes before rmx_learn_rng_seed)");
+  uint64_t* col = h->host ? h->host->learn_rng : h->learn_rng;
+  if (!col) return fail(RMX_E_STATE, "no generator column bound (rmx_learn_rng_bind)");
+  if (!seeds) return fail(RMX_E_INVALID, "seeds is NULL");
+  const int64_t n = (int64_t)h->cfg.n_agents * h->cfg.n_envs;
+  if (h->host) {
+    rmx::learn_rng_fill(seeds, n, col);
+    return RMX_OK;
+  }
+  std::vector<uint64_t> words;
+  try {
+    words.resize((size_t)n * 5);
+  } catch (const std::exception& e) {
+    return fail(RMX_E_INVALID, std::string("rmx_learn_rng_seed: ") + e.what());
+  }
+  rmx::learn_rng_fill(seeds, n, words.data());
+  SYNC_END_OR_RETURN(h);
+  HIP_TRY(hipSetDevice(h->device), "hipSetDevice");
+  // in stream order after the caller's earlier work; the staging copy lives until the copy has been made
+  HIP_TRY(hipMemcpyAsync(col, words.data(), sizeof(uint64_t) * words.size(), hipMemcpyHostToDevice, as_stream(stream)),
+          "generator column upload");
+  HIP_TRY(hipStreamSynchronize(as_stream(stream)), "generator column upload");
+  return RMX_OK;
+}
+
+static int do_learn_step(rmx_handle* h, const int32_t* actions, rmx::LearnCall lc, uint64_t seed, int64_t t_global,
+                         int autoreset, void* stream) {
   if (!h) return fail(RMX_E_INVALID, "handle is NULL");
   if (!h->bound) return fail(RMX_E_STATE, "buffers not bound (rmx_bind)");
   if (!(h->host ? h->host->learn_on : h->learn_on)) return fail(RMX_E_STATE, "no learner bound (rmx_learn_bind)");
   if (!lc.policy && !actions) return fail(RMX_E_INVALID, "actions is NULL");
+  if (lc.policy == rmx::kLearnNumpy) {
+    lc.rng = h->host ? h->host->learn_rng : h->learn_rng;
+    if (!lc.rng) return fail(RMX_E_STATE, "RMX_LEARN_NUMPY needs a generator column (rmx_learn_rng_bind)");
+  }
   if (h->host) {
     h->host->step(actions, autoreset, false, seed, t_global, nullptr, &lc);
     return RMX_OK;
@@ -1224,10 +1269,10 @@ int rmx_learn_step_policy(rmx_handle* h, double epsilon, int flags, uint64_t see
                           int32_t* actions_out, void* stream) {
   if (!h) return fail(RMX_E_INVALID, "handle is NULL");
   if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(RMX_E_INVALID, "epsilon must be in [0, 1]");
-  if (flags & ~(RMX_LEARN_UPDATE | RMX_LEARN_BEST)) return fail(RMX_E_INVALID, "unknown learn step flags");
+  if (flags & ~(RMX_LEARN_UPDATE | RMX_LEARN_BEST | RMX_LEARN_NUMPY)) return fail(RMX_E_INVALID, "unknown learn step flags");
   rmx::LearnCall lc{};
   lc.epsilon = epsilon;
-  lc.policy = 1;
+  lc.policy = (flags & RMX_LEARN_NUMPY) ? rmx::kLearnNumpy : rmx::kLearnHash;
   lc.update = (flags & RMX_LEARN_UPDATE) ? 1 : 0;
   lc.best = (flags & RMX_LEARN_BEST) ? 1 : 0;
   lc.actions_out = actions_out;

@@ -105,6 +105,17 @@ inline uint64_t cdf_threshold(double cdf) {  // Generator.random() = m * 2^-53: 
 
 }  // namespace
 
+void learn_rng_fill(const uint64_t* seeds, int64_t n, uint64_t* col) {
+  for (int64_t i = 0; i < n; ++i) {
+    const HostPcg r = seed_pcg64(seeds[i]);
+    col[i] = r.hi;
+    col[n + i] = r.lo;
+    col[2 * n + i] = r.ihi;
+    col[3 * n + i] = r.ilo;
+    col[4 * n + i] = 0;  // no 32-bit half buffered
+  }
+}
+
 std::string HostEngine::init(const rmx_config& c) {
   BlobOffsets bo;
   if (!build_table_blob(c, blob, bo)) return "tables exceed 64 KiB (the generic kernels' LDS blob)";
@@ -367,8 +378,19 @@ uint32_t HostEngine::step(const int32_t* actions, int autoreset, bool hashed, ui
         const double* row = (uint64_t)st < (uint64_t)((int64_t)cfg.width * cfg.height * enc_nq[a])
                                 ? learn.q + (((int64_t)a * N + e) * learn.s_max + st) * 4
                                 : none;
-        act[a] = learn_policy(seed, t_global, cfg.n_envs_global, cfg.env_offset + e, A, a, lc->epsilon, lc->best, row[0],
-                              row[1], row[2], row[3]);
+        if (lc->policy == kLearnNumpy && !lc->best) {  // the learner's own numpy generator (RMX_LEARN_NUMPY)
+          const int64_t plane = (int64_t)A * N;
+          uint64_t* w = lc->rng + (int64_t)a * N + e;
+          const uint64_t w4 = w[4 * plane];
+          LearnRng r = {w[0], w[plane], w[2 * plane], w[3 * plane], (uint32_t)(w4 >> 32), (uint32_t)w4};
+          act[a] = learn_policy_numpy(r, lc->epsilon, row[0], row[1], row[2], row[3]);
+          w[0] = r.hi;
+          w[plane] = r.lo;
+          if (learn_rng_word4(r) != w4) w[4 * plane] = learn_rng_word4(r);
+        } else {
+          act[a] = learn_policy(seed, t_global, cfg.n_envs_global, cfg.env_offset + e, A, a, lc->epsilon, lc->best,
+                                row[0], row[1], row[2], row[3]);
+        }
         if (lc->actions_out) lc->actions_out[(int64_t)a * N + e] = act[a];
       }
     }

@@ -72,6 +72,7 @@ struct HostEngine {
   LearnParams learn{};
   bool learn_on = false;
   std::vector<double> learn_phi;
+  uint64_t* learn_rng = nullptr;  // rmx_learn_rng_bind: the learners' numpy generators, caller's [5][A][N]
 
   // "" or the reason the config cannot run on the host path (after validate_config)
   std::string init(const rmx_config& c);
@@ -81,7 +82,8 @@ struct HostEngine {
   // rmx_step / rmx_step_hashed for every env: actions [A][N] host ints, or hashed (seed, t_global); returns 1 if an
   // action outside [0, 4] (or "wait" under FrozenLake slip) was stepped (as wait)
   // lc != NULL: a learn step (rmx_learn_step / rmx_learn_step_policy): the policy's actions when lc->policy (seed,
-  // t_global are then the policy hash's), the bound learner's update when lc->update
+  // t_global are then the policy hash's; lc->policy == kLearnNumpy: the learners' own generators in lc->rng), the
+  // bound learner's update when lc->update
   uint32_t step(const int32_t* actions, int autoreset, bool hashed = false, uint64_t seed = 0, int64_t t_global = 0,
                 float* trace = nullptr, const LearnCall* lc = nullptr);
   void fill_actions(uint64_t seed, int64_t t0, int32_t T, int32_t* out) const;
@@ -97,5 +99,9 @@ struct HostEngine {
   void random_starts(HostPcg& r, HostAgent* s);
   int32_t slip_choice(int32_t intended, HostPcg& r) const;
 };
+
+// rmx_learn_rng_seed: default_rng(seeds[i]) of n learners as a generator column [5][n] (state high, state low,
+// increment high, increment low, the buffer word: 0), on the host
+void learn_rng_fill(const uint64_t* seeds, int64_t n, uint64_t* col);
 
 }  // namespace rmx

@@ -10,6 +10,8 @@
 //   shaping           qlearning.py:93-105 (r += gamma * Phi(next) - Phi(prev), the learner's gamma)
 //   greedy ties       qlearning.py:137-143 (the maxima by equality with the row maximum, in index order), best:
 //                     np.argmax (qlearning.py:116-117)
+//   choose_action     qlearning.py:112-143 on the learner's own default_rng(seed) (learning_algorithm.py:32): the
+//                     explore test, Generator.choice for the explore action and among the maxima (learn_policy_numpy)
 // Every operation below is one IEEE float64 operation, in the reference's order: contraction into fused
 // multiply-adds is off for this file's arithmetic on both sides (hipcc contracts across statements by default).
 #pragma once
@@ -45,11 +47,13 @@ struct LearnParams {
 // Per-call arguments of a learn step.
 struct LearnCall {
   double epsilon;
-  int32_t policy;  // 0: the caller's actions; 1: the engine's policy (below)
+  int32_t policy;  // 0: the caller's actions; 1: the engine's policy; 2: the learners' numpy streams (both below)
   int32_t update;  // RMX_LEARN_UPDATE
   int32_t best;    // RMX_LEARN_BEST
   int32_t* actions_out;  // [A][N] or NULL (policy steps)
+  uint64_t* rng;         // policy 2: the generator column bound by rmx_learn_rng_bind, [5][A][N]
 };
+enum { kLearnActions = 0, kLearnHash = 1, kLearnNumpy = 2 };  // LearnCall::policy
 
 constexpr uint64_t kLearnGolden = 0x9E3779B97F4A7C15ull;
 
@@ -113,6 +117,81 @@ RMX_LEARN_HD int32_t learn_policy(uint64_t seed, int64_t t, int64_t n_global, in
   const int e0 = r0 == m, e1 = r1 == m, e2 = r2 == m, e3 = r3 == m;
   const uint64_t n_max = (uint64_t)(e0 + e1 + e2 + e3);
   int pick = (int)(((h2 >> 32) * n_max) >> 32);  // maximum number `pick`, in index order
+  if (e0 && pick-- == 0) return 0;
+  if (e1 && pick-- == 0) return 1;
+  if (e2 && pick-- == 0) return 2;
+  return 3;
+}
+
+// ---- the reference's own action stream: each learner's np.random.default_rng(seed) (learning_algorithm.py:32) as
+// QLearning.choose_action draws from it (qlearning.py:112-143) --------------------------------------------------------
+// Restated from numpy/random/src/pcg64/pcg64.h (pcg64_next64 / pcg64_next32: a 64-bit output serves two 32-bit draws,
+// low half first, the high half buffered in has_uint32 / uinteger; next64 never touches the buffer),
+// _generator.pyx (uniform(0, 1) = next_double; choice of a k-sequence = integers(0, k)) and distributions.c
+// (random_bounded_uint64 -> buffered_bounded_lemire_uint32 for ranges below 2^32; a range of one value draws nothing).
+struct LearnRng {
+  uint64_t hi, lo, ihi, ilo;  // 128-bit state, 128-bit increment
+  uint32_t has, u;            // has_uint32, uinteger
+};
+
+// The bound column (rmx_learn_rng_bind): uint64 [5][A][N], word w of learner (a, e) at ((w * A + a) * N + e)
+RMX_LEARN_HD uint64_t learn_rng_word4(const LearnRng& r) { return ((uint64_t)r.has << 32) | r.u; }
+
+RMX_LEARN_HD uint64_t learn_pcg_next64(LearnRng& r) {
+  constexpr uint64_t MH = 0x2360ED051FC65DA4ull, ML = 0x4385DF649FCCF645ull;
+  const uint64_t nlo = r.lo * ML;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint64_t carry = __umul64hi(r.lo, ML);
+#else
+  const uint64_t carry = (uint64_t)(((unsigned __int128)r.lo * ML) >> 64);
+#endif
+  const uint64_t nhi = carry + r.lo * MH + r.hi * ML;
+  const uint64_t slo = nlo + r.ilo;
+  r.hi = nhi + r.ihi + (slo < nlo ? 1ull : 0ull);
+  r.lo = slo;
+  const uint64_t x = r.hi ^ r.lo;  // XSL-RR of the new state
+  const unsigned rot = (unsigned)(r.hi >> 58);
+  return (x >> rot) | (x << ((64u - rot) & 63u));
+}
+
+RMX_LEARN_HD uint32_t learn_pcg_next32(LearnRng& r) {
+  if (r.has) {
+    r.has = 0;
+    return r.u;
+  }
+  const uint64_t v = learn_pcg_next64(r);
+  r.has = 1;
+  r.u = (uint32_t)(v >> 32);
+  return (uint32_t)v;
+}
+
+// integers(0, k), 1 <= k < 2^32: Lemire's method on buffered 32-bit draws.  The threshold is 2^32 mod k: 0 for k = 2
+// and 4, so of a row's tie counts only k = 3 can redraw, and only on a zero low half.
+RMX_LEARN_HD uint32_t learn_bounded(LearnRng& r, uint32_t k) {
+  if (k == 1u) return 0u;
+  uint64_t m = (uint64_t)learn_pcg_next32(r) * k;
+  uint32_t left = (uint32_t)m;
+  if (left < k) {
+    const uint32_t thr = (0xFFFFFFFFu - (k - 1u)) % k;
+    while (left < thr) {
+      m = (uint64_t)learn_pcg_next32(r) * k;
+      left = (uint32_t)m;
+    }
+  }
+  return (uint32_t)(m >> 32);
+}
+
+// choose_action on the learner's own generator (include/rmx.h, RMX_LEARN_NUMPY), over the row of the state the step is
+// about to leave.  The explore draw is taken whatever epsilon is; a row with no entry equal to its maximum (a NaN
+// maximum, where the reference raises) gives action 3 without a further draw.
+RMX_LEARN_HD int32_t learn_policy_numpy(LearnRng& r, double epsilon, double r0, double r1, double r2, double r3) {
+  const double d = (double)(learn_pcg_next64(r) >> 11) * 0x1p-53;
+  if (d < epsilon) return (int32_t)learn_bounded(r, 4u);
+  const double m = learn_max4(r0, r1, r2, r3);
+  const int e0 = r0 == m, e1 = r1 == m, e2 = r2 == m, e3 = r3 == m;
+  const uint32_t n_max = (uint32_t)(e0 + e1 + e2 + e3);
+  if (n_max == 0u) return 3;
+  int pick = (int)learn_bounded(r, n_max);  // maximum number `pick`, in index order
   if (e0 && pick-- == 0) return 0;
   if (e1 && pick-- == 0) return 1;
   if (e2 && pick-- == 0) return 2;

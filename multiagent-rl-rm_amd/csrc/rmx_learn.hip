@@ -10,6 +10,9 @@
 // entry, the visit count) and two 8-B stores.  The step is bound by these sub-line accesses to HBM, not by the chain:
 // having experience j of every agent in flight together was measured and was no faster.
 // Tables are float64 [A][N][S_max][4]; every index is int64.
+// With RMX_LEARN_NUMPY the thread also owns its learners' numpy generators (the column uint64 [5][A][N], plane-major:
+// each word a coalesced 8-B load per lane): it draws the reference's choose_action from them and stores the two state
+// words, and the buffer word when it changed.  Tail lanes and the agents past A of the 8-bucket touch nothing.
 //
 // Reference semantics: rmx_learn.h (update, experiences, policy), rmx_kernels.hip (the step).
 #include <hip/hip_runtime.h>
@@ -23,7 +26,9 @@
 
 namespace rmx {
 
-template <int KIND, int AMAX, bool POLICY>
+// POLICY: kLearnActions (the caller's actions), kLearnHash (the engine's hash policy) or kLearnNumpy (each learner's
+// numpy generator, read from and written back to lc.rng); everything the third adds sits behind if constexpr.
+template <int KIND, int AMAX, int POLICY>
 __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams lp, LearnCall lc) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int64_t N = p.N;
@@ -44,7 +49,7 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
         s[a].q = p.rm_q[k];
         s[a].f = p.flags[k];
         s[a].ret = p.ep_ret[k];
-        if constexpr (!POLICY) act[a] = p.actions[k];
+        if constexpr (POLICY == kLearnActions) act[a] = p.actions[k];
       }
     }
   }
@@ -74,8 +79,25 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
             lo = row[0];
             hi = row[1];
           }
-          act[a] = learn_policy(p.seed, p.t_global, p.n_global, p.env_offset + e, p.A, a, lc.epsilon, lc.best, lo.x,
-                                lo.y, hi.x, hi.y);
+          if constexpr (POLICY == kLearnNumpy) {
+            if (lc.best) {  // no draw: the column is not touched
+              act[a] = learn_policy(0, 0, 0, 0, p.A, a, lc.epsilon, 1, lo.x, lo.y, hi.x, hi.y);
+            } else {
+              // the learner's five words, plane-major: each a coalesced 8-B load per lane
+              const int64_t plane = (int64_t)p.A * N;
+              uint64_t* w = lc.rng + (int64_t)a * N + e;
+              const uint64_t w4 = w[4 * plane];
+              LearnRng r = {w[0], w[plane], w[2 * plane], w[3 * plane], (uint32_t)(w4 >> 32), (uint32_t)w4};
+              act[a] = learn_policy_numpy(r, lc.epsilon, lo.x, lo.y, hi.x, hi.y);
+              w[0] = r.hi;
+              w[plane] = r.lo;
+              const uint64_t n4 = learn_rng_word4(r);
+              if (n4 != w4) w[4 * plane] = n4;  // (the increment never changes)
+            }
+          } else {
+            act[a] = learn_policy(p.seed, p.t_global, p.n_global, p.env_offset + e, p.A, a, lc.epsilon, lc.best, lo.x,
+                                  lo.y, hi.x, hi.y);
+          }
           if (lc.actions_out) lc.actions_out[(int64_t)a * N + e] = act[a];
         }
       }
@@ -135,10 +157,12 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
 template <int KIND, int AMAX>
 static hipError_t launch_learn_t(const KParams& p, const LearnParams& lp, const LearnCall& lc, dim3 g, dim3 b,
                                  size_t lds, hipStream_t st) {
-  if (lc.policy)
-    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, true>), g, b, lds, st, p, lp, lc);
+  if (lc.policy == kLearnNumpy)
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnNumpy>), g, b, lds, st, p, lp, lc);
+  else if (lc.policy)
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnHash>), g, b, lds, st, p, lp, lc);
   else
-    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, false>), g, b, lds, st, p, lp, lc);
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnActions>), g, b, lds, st, p, lp, lc);
   return hipGetLastError();
 }
 

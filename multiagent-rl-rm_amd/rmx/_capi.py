@@ -29,8 +29,9 @@ EXPORTS = (
     "rmx_step_sync_begin", "rmx_sync_wait", "rmx_sync_end", "rmx_step_seq", "rmx_queue_counters", "rmx_queue_info",
     "rmx_code_object_check", "rmx_device_count", "rmx_queue_timing", "rmx_queue_times", "rmx_step_info",
     "rmx_seq_packed", "rmx_learn_states", "rmx_learn_bind", "rmx_learn_step", "rmx_learn_step_policy",
+    "rmx_learn_rng_bind", "rmx_learn_rng_seed",
 )
-LEARN_UPDATE, LEARN_BEST = 1, 2  # RMX_LEARN_*
+LEARN_UPDATE, LEARN_BEST, LEARN_NUMPY = 1, 2, 4  # RMX_LEARN_*
 SYNC_MAX_ENVS = 256  # RMX_SYNC_MAX_ENVS
 QUEUE_INFO_N = 7  # RMX_QUEUE_INFO_N
 QUEUE_STATES = ("unused", "ready", "unavailable", "retired")  # RMX_QUEUE_*
@@ -231,6 +232,8 @@ def load_library(path: str = None, check_source: bool = True):
         "rmx_learn_bind": (C.c_int, [vp, C.POINTER(RmxLearnConfig), vp, vp]),
         "rmx_learn_step": (C.c_int, [vp, vp, C.c_int, vp]),
         "rmx_learn_step_policy": (C.c_int, [vp, C.c_double, C.c_int, u64, i64, C.c_int, vp, vp]),
+        "rmx_learn_rng_bind": (C.c_int, [vp, vp]),
+        "rmx_learn_rng_seed": (C.c_int, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -21,10 +21,13 @@ class VecQLearning:
     """``q`` and ``visits``: ``[A, N, S_max, 4]`` float64, ``q[a, e]`` the ``q_table`` of agent a's learner in env e
     (rows past ``W*H*enc_nq[a]`` unused).  ``learning_rate=None`` is the reference's ``1 / visits`` rate.
     ``trunc_is_terminal=None`` follows the env kind: the FrozenLake runner passes ``done or truncated`` to the update,
-    the OfficeWorld runner ``done``."""
+    the OfficeWorld runner ``done``.  ``policy_seeds`` (an int, or an ``[A, N]`` array of learner seeds) gives every
+    learner the reference's own ``np.random.default_rng(seed)`` for ``act_step(reference_stream=True)``: ``rng`` is
+    then the generator column ``[5, A, N]`` (include/rmx.h; an int64 tensor holding the uint64 words on a GPU env, a
+    uint64 array on a host env)."""
 
     def __init__(self, env, gamma, learning_rate=None, qtable_init=1.0, use_qrm=False, use_rsh=False,
-                 trunc_is_terminal=None):
+                 trunc_is_terminal=None, policy_seeds=None):
         # argument checks before the tables are allocated (several GB on a GPU env)
         if learning_rate is not None and float(learning_rate) == 0.0:
             raise ValueError("learning_rate must be > 0, or None for 1 / visits")
@@ -61,6 +64,21 @@ class VecQLearning:
         _capi.check(self.lib.rmx_learn_bind(env._h, C.byref(cfg), ptr(self.q), ptr(self.visits)), "rmx_learn_bind")
         self.gamma, self.learning_rate = float(gamma), learning_rate
         self.use_qrm, self.use_rsh, self.trunc_is_terminal = bool(use_qrm), bool(use_rsh), bool(trunc_is_terminal)
+        self.rng = None
+        if policy_seeds is not None:
+            seeds = np.asarray(policy_seeds)
+            if seeds.dtype.kind not in "iu" or (seeds.dtype.kind == "i" and (seeds < 0).any()):
+                raise ValueError("policy_seeds must be non-negative integers")
+            seeds = np.ascontiguousarray(np.broadcast_to(seeds.astype(np.uint64), (env.A, env.N))) \
+                if seeds.ndim == 0 else np.ascontiguousarray(seeds, np.uint64)
+            if seeds.shape != (env.A, env.N):
+                raise ValueError(f"policy_seeds must be an int or [A={env.A}, N={env.N}]")
+            if self.host:
+                self.rng = np.zeros((5, env.A, env.N), np.uint64)
+            else:
+                self.rng = env.torch.zeros((5, env.A, env.N), dtype=env.torch.int64, device=env.device)
+            _capi.check(self.lib.rmx_learn_rng_bind(env._h, ptr(self.rng)), "rmx_learn_rng_bind")
+            _capi.check(self.lib.rmx_learn_rng_seed(env._h, seeds.ctypes.data, self._stream()), "rmx_learn_rng_seed")
 
     def _stream(self):
         return None if self.host else self.env._stream()
@@ -81,11 +99,19 @@ class VecQLearning:
             p = a.data_ptr()
         _capi.check(self.lib.rmx_learn_step(env._h, p, 1 if autoreset else 0, self._stream()), "rmx_learn_step")
 
-    def act_step(self, epsilon, seed, t_global, best=False, learn=True, autoreset=True, actions_out=None):
+    def act_step(self, epsilon, seed=None, t_global=None, best=False, learn=True, autoreset=True, actions_out=None,
+                 reference_stream=False):
         """One step with the engine's policy (epsilon-greedy over each learner's own row with hash-chosen ties;
         ``best``: np.argmax), and with ``learn`` the update.  ``actions_out``: an [A, N] int32 array / tensor that
-        receives the chosen actions."""
+        receives the chosen actions.  ``reference_stream``: the reference's ``choose_action`` on each learner's own
+        numpy generator instead (``policy_seeds``); ``seed`` and ``t_global`` are then unused and may be ``None``."""
         env = self.env
+        if reference_stream:
+            if self.rng is None:
+                raise RuntimeError("act_step(reference_stream=True) needs policy_seeds at construction")
+            seed = t_global = 0
+        elif seed is None or t_global is None:
+            raise ValueError("the engine's policy needs seed and t_global")
         p = None
         if actions_out is not None:
             if self.host:
@@ -96,11 +122,42 @@ class VecQLearning:
                         not actions_out.is_contiguous() or actions_out.numel() < env.A * env.N:
                     raise ValueError("actions_out must be a contiguous int32 [A, N] tensor on the engine's device")
                 p = actions_out.data_ptr()
-        flags = (_capi.LEARN_UPDATE if learn else 0) | (_capi.LEARN_BEST if best else 0)
+        flags = (_capi.LEARN_UPDATE if learn else 0) | (_capi.LEARN_BEST if best else 0) | \
+            (_capi.LEARN_NUMPY if reference_stream else 0)
         _capi.check(self.lib.rmx_learn_step_policy(env._h, float(epsilon), flags, int(seed) & (2**64 - 1),
                                                    int(t_global), 1 if autoreset else 0, p, self._stream()),
                     "rmx_learn_step_policy")
         return actions_out
+
+    def rng_state(self, a, e):
+        """Learner (a, e)'s generator as numpy's own ``bit_generator.state`` dict (hand it to a real ``Generator``)."""
+        if self.rng is None:
+            raise RuntimeError("no generator column (policy_seeds)")
+        if self.host:
+            w = [int(v) for v in self.rng[:, a, e]]
+        else:
+            self.env.sync_end()
+            w = [int(v) & (2**64 - 1) for v in self.rng[:, a, e].cpu().numpy()]
+        return {"bit_generator": "PCG64", "state": {"state": (w[0] << 64) | w[1], "inc": (w[2] << 64) | w[3]},
+                "has_uint32": w[4] >> 32, "uinteger": w[4] & 0xFFFFFFFF}
+
+    def set_rng_state(self, a, e, state):
+        """Set learner (a, e)'s generator from a ``bit_generator.state`` dict of a PCG64."""
+        if self.rng is None:
+            raise RuntimeError("no generator column (policy_seeds)")
+        if state.get("bit_generator") != "PCG64":
+            raise ValueError("the learners' generators are PCG64")
+        st, inc = int(state["state"]["state"]), int(state["state"]["inc"])
+        has, u = int(state["has_uint32"]), int(state["uinteger"])
+        if not (0 <= st < 2**128 and 0 <= inc < 2**128 and has in (0, 1) and 0 <= u < 2**32):
+            raise ValueError("not a PCG64 state")
+        m = 2**64 - 1
+        w = np.array([st >> 64, st & m, inc >> 64, inc & m, (has << 32) | u], np.uint64)
+        if self.host:
+            self.rng[:, a, e] = w
+        else:
+            self.env.sync_end()
+            self.rng[:, a, e] = self.env.torch.from_numpy(w.view(np.int64)).to(self.env.device)
 
     def greedy(self):
         """np.argmax of every learner's row at its env's current state: [A, N] (numpy int64 / torch int64)."""
