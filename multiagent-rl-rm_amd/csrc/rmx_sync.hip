@@ -11,7 +11,7 @@
 // its own memory.  Each side only reads memory local to it in its poll loop.
 //
 // Lifetime: the workgroup exits on an exit request, after idle_ticks without a request (the host relaunches on
-// the next call; rmx_capi.cpp), or after life_ticks in all.  Every wave leaves the loop together (the request
+// the next call; rmx_capi_sync.cpp), or after life_ticks in all.  Every wave leaves the loop together (the request
 // word is broadcast through LDS), and on exit writes its state back to the bound device columns, so the
 // asynchronous entry points (which end the resident workgroup first) continue from it.
 #include <hip/hip_runtime.h>

@@ -53,7 +53,9 @@ ABI_VERSION = 12  # include/rmx.h RMX_ABI_VERSION
 # list as RMX_HASHED in csrc/Makefile (tests/test_capi.py checks that they agree).
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
 HASHED_SOURCES = ("rmx_kernels.hip", "rmx_fast.hip", "rmx_fast_step.inc", "rmx_sync.hip", "rmx_capi.cpp",
-                  "rmx_queue.cpp", "rmx_tables.cpp", "rmx_comd.cpp", "rmx_build_info.cpp", "rmx_internal.h", "rmx_layout.h", "rmx_host.h", "rmx_device.h",
+                  "rmx_queue.cpp", "rmx_tables.cpp",
+                  "rmx_handle.h", "rmx_capi_create.cpp", "rmx_capi_sync.cpp", "rmx_capi_seq.cpp", "rmx_capi_learn.cpp", "rmx_capi_state.cpp",
+                  "rmx_comd.cpp", "rmx_build_info.cpp", "rmx_internal.h", "rmx_layout.h", "rmx_host.h", "rmx_device.h",
                   "rmx_generic.h", "rmx_comd.h", "rmx_hoststep.cpp", "rmx_hoststep.h", "rmx_learn.hip", "rmx_learn.h",
                   "../../include/rmx.h",
                   "Makefile")

@@ -49,6 +49,21 @@ def test_hashed_source_list_matches_makefile():
     assert files == _capi.HASHED_SOURCES
 
 
+def test_every_compiled_source_is_hashed():
+    """Every file the Makefile compiles into librmx.so (SRCS) or makes its objects depend on (HEADERS) is in
+    RMX_HASHED: a source left out of the digest would let load_library accept a stale build."""
+    mk = open(os.path.join(_capi.CSRC, "Makefile")).read()
+    var = {}
+    for name in ("HOST_SRCS", "SRCS", "HEADERS", "RMX_HASHED"):
+        m = re.search(r"^%s := (.*?)(?<!\\)\n" % name, mk, flags=re.S | re.M)
+        if name == "HOST_SRCS" and not m:  # (a Makefile that spells SRCS out in full)
+            continue
+        words = m.group(1).replace("\\\n", " ").split()
+        var[name] = [w for x in words for w in (var[x[2:-1]] if x.startswith("$(") else [x])]
+    assert len(var["SRCS"]) >= 9 and len(var["HEADERS"]) >= 10
+    assert set(var["SRCS"]) | set(var["HEADERS"]) <= set(var["RMX_HASHED"])
+
+
 def test_library_built_from_this_tree():
     """Provenance: the in-tree librmx.so reports the SHA-256 digest of exactly the sources in this tree
     (load_library refuses anything else), so a green GPU run can only come from a HEAD build."""

@@ -788,7 +788,7 @@ def size_world(W, H, A, Q, n_ev=2, same_rm=True, shaping=False, kind=T.FROZEN_LA
 
 SIZE_EDGES = {
     # name: (size_world arguments, forced mode, (variant, tables, sections, 16-B record bytes))
-    # the default keeps the merged table while it is at most 128 KiB (rmx_capi.cpp kFastMergedDefaultBytes)
+    # the default keeps the merged table while it is at most 128 KiB (rmx_handle.h kFastMergedDefaultBytes)
     "merged_default_under": (dict(W=21, H=13, A=1, Q=6), "default", ("fast", "merged4", 1, 131040)),
     "merged_default_over": (dict(W=137, H=2, A=1, Q=6), "default", ("fast", "global", 0, 0)),
     # (64 KiB is no threshold of the default: both sides of it run the 4-B records)

@@ -95,7 +95,7 @@ def test_undo_full_and_chain_give_the_first_slots(n, A):
 
 
 def test_jump_ahead_matches_numpy_state():
-    """rs_jump: M^j and the geometric sum, as the host builds them (rmx_capi.cpp RsJumpTable), for j = 1..64."""
+    """rs_jump: M^j and the geometric sum, as the host builds them (rmx_capi_create.cpp RsJumpTable), for j = 1..64."""
     mj, sj, table = 1, 0, []
     for _ in range(64):
         sj = (sj + mj) % MOD

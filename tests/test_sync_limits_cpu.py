@@ -326,7 +326,7 @@ def run_qrm_refused(make, tab, stream=lambda env: None):
 
 # ---- D. the two halves ----------------------------------------------------------------------------------------------
 def run_two_halves(make, tab, acts, stream=lambda env: None, async_step=None):
-    """rmx_step_sync_begin, host work, rmx_sync_wait = rmx_step_sync; the error contract of csrc/rmx_capi.cpp:
+    """rmx_step_sync_begin, host work, rmx_sync_wait = rmx_step_sync; the error contract of csrc/rmx_capi_sync.cpp:
     rmx_sync_wait with nothing outstanding and a second begin are RMX_E_STATE, the pending request stays served
     exactly once; rmx_sync_end serves a begun request and drops its outputs.  async_step(env, actions) (device
     handles): an asynchronous entry point while a request is pending ends the resident workgroup first, which serves

@@ -1,5 +1,5 @@
 """The resident workgroup behind rmx_reset_sync / rmx_step_sync / rmx_step_sync_begin + rmx_sync_wait
-(csrc/rmx_sync.hip, driven by sync_setup / sync_begin / sync_copy_out in csrc/rmx_capi.cpp) and mdp_kernel at the
+(csrc/rmx_sync.hip, driven by sync_setup / sync_begin / sync_copy_out in csrc/rmx_capi_sync.cpp) and mdp_kernel at the
 engine's limits.
 
 What only this path has, and where it is put under test here:
