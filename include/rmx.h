@@ -374,8 +374,22 @@ int rmx_step_info(const rmx_handle* h, int64_t* out, int32_t n);
  * Every agent updates every step, inactive and RM-final ones included, as the runners do.  An action without a table
  * column (RMX_WAIT, or an invalid one, reported as rmx_step reports it) is stepped and updates nothing.
  * use_rsh without use_qrm is refused: the reference's own non-QRM shaping looks a label-keyed dict up by RM index
- * (agent_rl.py:158-165, qlearning.py:60-66), which is not reproduced.  The learn step serves deterministic dynamics
- * and fixed starts: a config with cfg.stochastic or cfg.random_starts is refused.
+ * (agent_rl.py:158-165, qlearning.py:60-66), which is not reproduced.
+ * Dynamics (rmx_learn_config.dynamics): RMX_LEARN_DYN_FIXED (0, a zeroed config) serves deterministic dynamics and
+ * fixed starts only: a config with cfg.stochastic or cfg.random_starts is refused.  RMX_LEARN_DYN_ENV follows the
+ * handle: on a handle with cfg.stochastic and / or cfg.random_starts (office_main.py --stochastic, ma_frozen_lake.py:
+ * 59-64 frozen_lake_stochastic / random_start_positions; rng and episode bound at rmx_bind as rmx_step needs them) the
+ * learn step does, per env and in the order of the runner's loop:
+ *   1. the auto-reset: for an env that resets, episode += 1, the env generator becomes default_rng(seed of that
+ *      episode in the seed schedule), and the random starts are drawn from it, before any slip draw;
+ *   2. the policy for every agent, frozen ones included, over the row of the state about to be left (the fresh,
+ *      possibly random, start after a reset); it draws from the learner's own generator only;
+ *   3. the step: the slip draws come from the env generator, in agent order, only for the agents that move;
+ *   4. the update, with the INTENDED action (the policy's or the caller's, not the slipped one) and the state actually
+ *      reached, as rm_environment_wrapper.py:140-183 and the runners hand them to update_policy.
+ * The env generator (rng [4][N]) and the learner generators (rmx_learn_rng_bind) never mix: neither is drawn from
+ * where the reference draws from the other.  On a deterministic handle RMX_LEARN_DYN_ENV runs the very kernels of
+ * RMX_LEARN_DYN_FIXED.
  * Bit-exactness: q equals the reference's bit for bit whenever every reward, penalty and reward_modifier of the
  * scenario is a float32 value (the engine stores them as float32).
  * The engine's policy (rmx_learn_step_policy; its own, not numpy's stream; independent of the sharding), chosen after
@@ -409,10 +423,13 @@ int rmx_step_info(const rmx_handle* h, int64_t* out, int32_t n);
  *   With RMX_LEARN_BEST as well, best wins: nothing is drawn and the column is not touched.  Without
  *   RMX_LEARN_UPDATE the draws still happen (select_action without update_policy).
  * Bit-exactness of a run: with epsilon fixed (the runners never call learn_done_episode, so epsilon stays at
- * epsilon_start), deterministic dynamics and fixed starts (all the learn step serves) and float32 rewards as above,
- * the actions of every step, q, visits and each generator's state after T steps equal those of the runner's loop
- * (select_action for every agent, rm_env.step, update_policy for every agent) bit for bit, on the device and on the
- * host, whatever the sharding (a learner's stream depends on its own column words only).
+ * epsilon_start) and float32 rewards as above, the actions of every step, q, visits and each generator's state after T
+ * steps equal those of the runner's loop (select_action for every agent, rm_env.step, update_policy for every agent)
+ * bit for bit, on the device and on the host, whatever the sharding (a learner's stream depends on its own column
+ * words only).  With RMX_LEARN_DYN_ENV this holds on slip and random-start worlds too, whose episodes the loop resets
+ * with the seed schedule's seeds (rmx_reset, cfg.seed_*): the env columns, the env generator and the episode count then
+ * equal the reference env's state, its rng.bit_generator.state and its number of resets as well (an env's stream
+ * depends on the base seed, its global index and its episode only).
  * The generator column is caller-owned like q and visits: uint64 rng[5][A][N], plane-major, word w of learner (a, e)
  * at rng[(w*A + a)*N + e]: 0 state high, 1 state low, 2 increment high, 3 increment low (numpy's bit_generator.state
  * "state" / "inc" as 128-bit numbers), 4 (has_uint32 << 32) | uinteger.  A learn step reads a learner's five words
@@ -429,15 +446,17 @@ int rmx_step_info(const rmx_handle* h, int64_t* out, int32_t n);
  * rmx_learn_bind copies phi (host [A][Q], Q = cfg.n_rm_states; required with use_rsh) and keeps q / visits
  * (visits: NULL unless learning_rate == 0 or the counts are wanted).  RMX_E_INVALID with a message, before any device
  * work: a NULL handle / config / q, gamma or learning_rate not finite or negative, no enc_nq, use_qrm with
- * n_qrm_max == 0, use_rsh without use_qrm or phi, 1/visits without visits, cfg.stochastic / cfg.random_starts,
- * epsilon outside [0, 1], unknown flags.  A learn step before rmx_bind or rmx_learn_bind: RMX_E_STATE.
+ * n_qrm_max == 0, use_rsh without use_qrm or phi, 1/visits without visits, a dynamics value other than the two below,
+ * cfg.stochastic / cfg.random_starts under RMX_LEARN_DYN_FIXED, epsilon outside [0, 1], unknown flags.  A learn step before rmx_bind or rmx_learn_bind: RMX_E_STATE.
  * Not served: rmx_step_seq windows (learn steps are stream launches), the dict API, the tables in rmx_get_state
  * (they are the caller's). */
 typedef struct rmx_learn_config {
   double gamma, learning_rate /* 0: 1/visits */;
-  int32_t use_qrm, use_rsh, trunc_is_terminal, reserved;
+  int32_t use_qrm, use_rsh, trunc_is_terminal, dynamics /* RMX_LEARN_DYN_* */;
   const double* phi; /* host [A][Q], required with use_rsh; copied */
 } rmx_learn_config;
+#define RMX_LEARN_DYN_FIXED 0 /* deterministic dynamics and fixed starts only (slip / random-start handles refused) */
+#define RMX_LEARN_DYN_ENV 1   /* the handle's dynamics: slip, the per-episode reseed and random starts included */
 #define RMX_LEARN_UPDATE 1
 #define RMX_LEARN_BEST 2
 #define RMX_LEARN_NUMPY 4 /* rmx_learn_step_policy: the reference's policy on the learners' own numpy generators */

@@ -30,6 +30,8 @@ static int do_learn_step(rmx_handle* h, const int32_t* actions, rmx::LearnCall l
   p.seed = seed;
   p.t_global = t_global;
   p.autoreset = autoreset ? 1 : 0;
+  // slip / random starts (a learner bound with RMX_LEARN_DYN_ENV): the kernel reads and writes the env generator and
+  // episode columns rmx_bind required, and none of the fast path's caches (the reset cache, the next-episode shuffles)
   HIP_TRY(rmx::launch_learn_step(p, h->learn.params, lc, h->cfg.kind, h->tables_bytes, as_stream(stream)), "learn step launch");
   return RMX_OK;
 }
@@ -62,7 +64,9 @@ int rmx_learn_bind(rmx_handle* h, const rmx_learn_config* lc, double* q, double*
                                "label-keyed dict by index)");
   if (lc->use_rsh && !lc->phi) return fail(RMX_E_INVALID, "use_rsh needs phi (the RM potentials by RM index)");
   if (lc->learning_rate == 0.0 && !visits) return fail(RMX_E_INVALID, "the 1 / visits learning rate needs a visits table");
-  if (h->cfg.stochastic || h->cfg.random_starts)
+  if (lc->dynamics != RMX_LEARN_DYN_FIXED && lc->dynamics != RMX_LEARN_DYN_ENV)
+    return fail(RMX_E_INVALID, "dynamics must be RMX_LEARN_DYN_FIXED or RMX_LEARN_DYN_ENV");
+  if (lc->dynamics == RMX_LEARN_DYN_FIXED && (h->cfg.stochastic || h->cfg.random_starts))
     return fail(RMX_E_INVALID, "the learn step serves deterministic dynamics and fixed starts (cfg.stochastic / "
                                "cfg.random_starts are set)");
   rmx::LearnParams lp{};

@@ -13,6 +13,11 @@
 // With RMX_LEARN_NUMPY the thread also owns its learners' numpy generators (the column uint64 [5][A][N], plane-major:
 // each word a coalesced 8-B load per lane): it draws the reference's choose_action from them and stores the two state
 // words, and the buffer word when it changed.  Tail lanes and the agents past A of the 8-bucket touch nothing.
+// With STOCH (a handle with slip and / or random starts under RMX_LEARN_DYN_ENV) the thread also owns its env's numpy
+// generator, as step_kernel's STOCH does (the rng column uint64 [4][N], the episode column): the auto-reset reseeds it
+// from the seed schedule and draws the random starts before the policy reads its rows, the step draws the slips from
+// it, and the four words are stored after the step.  The learners' draws all come before the first slip draw and the
+// two kinds of generator never mix.  Tail lanes touch neither column.
 //
 // Reference semantics: rmx_learn.h (update, experiences, policy), rmx_kernels.hip (the step).
 #include <hip/hip_runtime.h>
@@ -28,7 +33,8 @@ namespace rmx {
 
 // POLICY: kLearnActions (the caller's actions), kLearnHash (the engine's hash policy) or kLearnNumpy (each learner's
 // numpy generator, read from and written back to lc.rng); everything the third adds sits behind if constexpr.
-template <int KIND, int AMAX, int POLICY>
+// STOCH: the env's own generator (slip, the per-episode reseed, random starts), likewise behind if constexpr.
+template <int KIND, int AMAX, int POLICY, bool STOCH>
 __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams lp, LearnCall lc) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int64_t N = p.N;
@@ -63,7 +69,17 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
   uint32_t bad = 0;
   AgentOut o[AMAX];
   if (live) {
-    if (p.autoreset && (s[0].f & RMX_F_ENV_DONE)) reset_regs<AMAX>(s, t, p);
+    Pcg rng = {0, 0, 0, 0};
+    if constexpr (STOCH) rng = {p.rng[e], p.rng[N + e], p.rng[2 * N + e], p.rng[3 * N + e]};
+    if (p.autoreset && (s[0].f & RMX_F_ENV_DONE)) {
+      reset_regs<AMAX>(s, t, p);
+      if constexpr (STOCH) {  // env.rng = default_rng(seed of the next episode)
+        const int32_t k = p.episode[e] + 1;
+        p.episode[e] = k;
+        rng = seed_pcg64(seed_of(p, p.env_offset + e, k));
+        if (p.random_starts) random_starts<AMAX>(p, rng, e, s);  // before the policy's row read and any slip draw
+      }
+    }
     // the RM state the step is about to leave; the policy reads that state's row
     int32_t q_pre[AMAX];
 #pragma unroll
@@ -103,7 +119,13 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
       }
     }
     const float disc = p.gamma_is_one ? 1.0f : p.disc[min((uint32_t)t, (uint32_t)p.max_t + 1u)];
-    done = env_step<KIND, AMAX>(s, t, act, L, p, disc, o, ls, &bad, nullptr);
+    done = env_step<KIND, AMAX>(s, t, act, L, p, disc, o, ls, &bad, STOCH ? &rng : nullptr);
+    if constexpr (STOCH) {
+      p.rng[e] = rng.hi;
+      p.rng[N + e] = rng.lo;
+      p.rng[2 * N + e] = rng.ihi;
+      p.rng[3 * N + e] = rng.ilo;
+    }
     p.t[e] = t;
     if (p.env_done) p.env_done[e] = (uint8_t)done;
 #pragma unroll
@@ -154,36 +176,41 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
   wave_flush_slot(p.slab, slot, ls, __any(done));
 }
 
-template <int KIND, int AMAX>
+template <int KIND, int AMAX, bool STOCH>
 static hipError_t launch_learn_t(const KParams& p, const LearnParams& lp, const LearnCall& lc, dim3 g, dim3 b,
                                  size_t lds, hipStream_t st) {
   if (lc.policy == kLearnNumpy)
-    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnNumpy>), g, b, lds, st, p, lp, lc);
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnNumpy, STOCH>), g, b, lds, st, p, lp, lc);
   else if (lc.policy)
-    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnHash>), g, b, lds, st, p, lp, lc);
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnHash, STOCH>), g, b, lds, st, p, lp, lc);
   else
-    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnActions>), g, b, lds, st, p, lp, lc);
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnActions, STOCH>), g, b, lds, st, p, lp, lc);
   return hipGetLastError();
 }
 
-template <int KIND>
+template <int KIND, bool STOCH>
 static hipError_t launch_learn_k(const KParams& p, const LearnParams& lp, const LearnCall& lc, dim3 g, dim3 b,
                                  size_t lds, hipStream_t st) {
   switch (amax_bucket(p.A)) {
-    case 1: return launch_learn_t<KIND, 1>(p, lp, lc, g, b, lds, st);
-    case 2: return launch_learn_t<KIND, 2>(p, lp, lc, g, b, lds, st);
-    case 3: return launch_learn_t<KIND, 3>(p, lp, lc, g, b, lds, st);
-    case 4: return launch_learn_t<KIND, 4>(p, lp, lc, g, b, lds, st);
-    default: return launch_learn_t<KIND, 8>(p, lp, lc, g, b, lds, st);
+    case 1: return launch_learn_t<KIND, 1, STOCH>(p, lp, lc, g, b, lds, st);
+    case 2: return launch_learn_t<KIND, 2, STOCH>(p, lp, lc, g, b, lds, st);
+    case 3: return launch_learn_t<KIND, 3, STOCH>(p, lp, lc, g, b, lds, st);
+    case 4: return launch_learn_t<KIND, 4, STOCH>(p, lp, lc, g, b, lds, st);
+    default: return launch_learn_t<KIND, 8, STOCH>(p, lp, lc, g, b, lds, st);
   }
 }
 
-// 256-thread blocks, one thread per env (the per-wave statistics slab is sized for that geometry at rmx_create)
+// 256-thread blocks, one thread per env (the per-wave statistics slab is sized for that geometry at rmx_create).
+// p.rng_on (the handle has slip or random starts; the caller has checked the learner's dynamics and the rng / episode
+// columns) selects the STOCH instantiations; every other handle runs the kernels it always ran.
 hipError_t launch_learn_step(const KParams& p, const LearnParams& lp, const LearnCall& lc, int kind, size_t lds,
                              hipStream_t st) {
   const dim3 g((unsigned)((p.N + 255) / 256)), b(256);
-  return kind == RMX_FROZEN_LAKE ? launch_learn_k<RMX_FROZEN_LAKE>(p, lp, lc, g, b, lds, st)
-                                 : launch_learn_k<RMX_OFFICE_WORLD>(p, lp, lc, g, b, lds, st);
+  if (p.rng_on)
+    return kind == RMX_FROZEN_LAKE ? launch_learn_k<RMX_FROZEN_LAKE, true>(p, lp, lc, g, b, lds, st)
+                                   : launch_learn_k<RMX_OFFICE_WORLD, true>(p, lp, lc, g, b, lds, st);
+  return kind == RMX_FROZEN_LAKE ? launch_learn_k<RMX_FROZEN_LAKE, false>(p, lp, lc, g, b, lds, st)
+                                 : launch_learn_k<RMX_OFFICE_WORLD, false>(p, lp, lc, g, b, lds, st);
 }
 
 }  // namespace rmx

@@ -32,6 +32,7 @@ EXPORTS = (
     "rmx_learn_rng_bind", "rmx_learn_rng_seed",
 )
 LEARN_UPDATE, LEARN_BEST, LEARN_NUMPY = 1, 2, 4  # RMX_LEARN_*
+LEARN_DYN_FIXED, LEARN_DYN_ENV = 0, 1  # rmx_learn_config.dynamics
 SYNC_MAX_ENVS = 256  # RMX_SYNC_MAX_ENVS
 QUEUE_INFO_N = 7  # RMX_QUEUE_INFO_N
 QUEUE_STATES = ("unused", "ready", "unavailable", "retired")  # RMX_QUEUE_*
@@ -97,7 +98,7 @@ class RmxConfig(C.Structure):
 
 class RmxLearnConfig(C.Structure):
     _fields_ = [("gamma", C.c_double), ("learning_rate", C.c_double), ("use_qrm", C.c_int32), ("use_rsh", C.c_int32),
-                ("trunc_is_terminal", C.c_int32), ("reserved", C.c_int32), ("phi", C.c_void_p)]
+                ("trunc_is_terminal", C.c_int32), ("dynamics", C.c_int32), ("phi", C.c_void_p)]
 
 
 class RmxBuffers(C.Structure):

@@ -6,6 +6,12 @@ office_main.py:1709-1749): N replicas of the runner's experiment in one process,
 with the reference's ``q_table`` (include/rmx.h, "tabular Q-learning / QRM learners").  On a ``VecRMEnv`` the tables
 are torch tensors on the engine's GPU and a learn step is one kernel launch (csrc/rmx_learn.hip); on a ``HostRMEnv``
 they are numpy arrays and the host path runs the same arithmetic (csrc/rmx_learn.h).
+
+The learners follow the env's dynamics (``RMX_LEARN_DYN_ENV``): on an env built from a slip (``stochastic``) or
+random-start scenario a learn step reseeds the env's generator at every auto-reset, draws the random starts, chooses
+the actions from the fresh start's rows, draws the slips and updates with the intended action and the state actually
+reached, in the runner's order; the env's generator and the learners' own never mix.  Whole reference training runs
+on such worlds are reproduced bit for bit, the env's generator and episode count included (tests/golden/slearn_*.npz).
 """
 from __future__ import annotations
 
@@ -61,6 +67,7 @@ class VecQLearning:
         cfg.learning_rate = 0.0 if learning_rate is None else float(learning_rate)
         cfg.use_qrm, cfg.use_rsh, cfg.trunc_is_terminal = int(bool(use_qrm)), int(bool(use_rsh)), int(bool(trunc_is_terminal))
         cfg.phi = None if self._phi is None else self._phi.ctypes.data
+        cfg.dynamics = _capi.LEARN_DYN_ENV  # slip and random starts as the env has them (deterministic: no difference)
         _capi.check(self.lib.rmx_learn_bind(env._h, C.byref(cfg), ptr(self.q), ptr(self.visits)), "rmx_learn_bind")
         self.gamma, self.learning_rate = float(gamma), learning_rate
         self.use_qrm, self.use_rsh, self.trunc_is_terminal = bool(use_qrm), bool(use_rsh), bool(trunc_is_terminal)
