@@ -32,7 +32,7 @@ int create_host(const rmx_config* cfg, rmx_handle** out) {
   h->cfg = h->host->cfg;  // scalars only
   h->device = RMX_DEVICE_HOST;
   h->digest = rmx::config_digest(*cfg);
-  for (int a = 0; a < cfg->n_agents; ++a) h->enc_nq[a] = h->host->enc_nq[a];
+  for (int a = 0; a < cfg->n_agents; ++a) h->enc_nq[a] = h->host->p.enc_nq[a];
   *out = h;
   return RMX_OK;
 }

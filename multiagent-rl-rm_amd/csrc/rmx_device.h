@@ -1,59 +1,14 @@
-// rmx_device.h — device helpers shared by the gfx950 kernels (action hash, per-wave statistics).
+// rmx_device.h — device-only helpers shared by the gfx950 kernels: the random-start shuffle over a workspace row, the
+// slip choice in its uniform-value (readfirstlane) form, per-wave statistics.  The action hash, numpy's generator
+// (Pcg, pcg_next64, seed_pcg64, seed_of) and the step rules are in rmx_rules.h, shared with the host path.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "rmx_internal.h"
+#include "rmx_rules.h"
 
 namespace rmx {
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  uint64_t z = x + kGolden;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// a = splitmix64(seed ^ (((t*N + e)*A + i) * GR)) >> 62
-__device__ __forceinline__ int32_t hash_action(uint64_t seed, int64_t t, int64_t n_global, int64_t e, int A, int i) {
-  uint64_t ctr = (((uint64_t)t * (uint64_t)n_global + (uint64_t)e) * (uint64_t)A + (uint64_t)i) * kGolden;
-  return (int32_t)(splitmix64(seed ^ ctr) >> 62);
-}
-
-// ---- numpy default_rng(seed) on the device: SeedSequence -> PCG64 (XSL-RR 128/64) ----------------
-// Restated from numpy/random/bit_generator.pyx (SeedSequence.mix_entropy / generate_state) and pcg64.h
-// (pcg_setseq_128_srandom_r, pcg_setseq_128_xsl_rr_64_random_r); Generator.random = (next64 >> 11) * 2^-53.
-struct Pcg {
-  uint64_t hi, lo, ihi, ilo;  // 128-bit state, 128-bit increment
-};
-
-__device__ __forceinline__ void pcg_step(Pcg& r) {
-  constexpr uint64_t MH = 0x2360ED051FC65DA4ull, ML = 0x4385DF649FCCF645ull;
-  const uint64_t nlo = r.lo * ML;
-  const uint64_t nhi = __umul64hi(r.lo, ML) + r.lo * MH + r.hi * ML;
-  const uint64_t slo = nlo + r.ilo;
-  r.hi = nhi + r.ihi + (slo < nlo ? 1ull : 0ull);
-  r.lo = slo;
-}
-
-__device__ __forceinline__ uint64_t pcg_next64(Pcg& r) {
-  pcg_step(r);
-  const uint64_t x = r.hi ^ r.lo;
-  const unsigned rot = (unsigned)(r.hi >> 58);
-  return (x >> rot) | (x << ((64u - rot) & 63u));
-}
-
-__device__ __forceinline__ uint32_t ss_hashmix(uint32_t v, uint32_t& hc) {
-  v ^= hc;
-  hc *= 0x931e8875u;
-  v *= hc;
-  return v ^ (v >> 16);
-}
-
-__device__ __forceinline__ uint32_t ss_mix(uint32_t x, uint32_t y) {
-  const uint32_t r = 0xca01f9ddu * x - 0x4973f715u * y;
-  return r ^ (r >> 16);
-}
 
 // FrozenLake random_start_positions (ma_frozen_lake.py:59-64, 156-172): rng.shuffle(free_cells) of a Python list
 // = numpy's untyped Generator.shuffle: Fisher-Yates from the end, for i = n-1 .. 1 swap(L[i], L[j_i]) with
@@ -115,45 +70,6 @@ __device__ __forceinline__ void shuffle_slots(Pcg& r, int32_t n, uint16_t* __res
     cur = nxt;
     nxt = nn;
   }
-}
-
-__device__ inline Pcg seed_pcg64(uint64_t seed) {
-  uint32_t ent0 = (uint32_t)seed, ent1 = (uint32_t)(seed >> 32);
-  const int n = (seed >> 32) ? 2 : 1;  // _coerce_to_uint32_array: little-endian 32-bit words (0 -> [0])
-  uint32_t pool[4], hc = 0x43b0d7e5u;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) pool[i] = ss_hashmix(i == 0 ? ent0 : (i == 1 && n == 2) ? ent1 : 0u, hc);
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-      if (s != d) pool[d] = ss_mix(pool[d], ss_hashmix(pool[s], hc));
-  uint32_t w[8], hb = 0x8b51f9ddu;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    uint32_t x = pool[i & 3] ^ hb;
-    hb *= 0x58f38dedu;
-    x *= hb;
-    w[i] = x ^ (x >> 16);
-  }
-  const uint64_t v0 = (uint64_t)w[0] | ((uint64_t)w[1] << 32), v1 = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
-  const uint64_t v2 = (uint64_t)w[4] | ((uint64_t)w[5] << 32), v3 = (uint64_t)w[6] | ((uint64_t)w[7] << 32);
-  Pcg r;
-  r.ihi = (v2 << 1) | (v3 >> 63);  // inc = (initseq << 1) | 1
-  r.ilo = (v3 << 1) | 1ull;
-  r.hi = 0;
-  r.lo = 0;
-  pcg_step(r);  // state = 0*M + inc
-  const uint64_t lo = r.lo + v1;  // state += initstate
-  r.hi = r.hi + v0 + (lo < r.lo ? 1ull : 0ull);
-  r.lo = lo;
-  pcg_step(r);
-  return r;
-}
-
-template <typename P>  // KParams (generic kernels) or FastParams (FrozenLake slip on the fast path)
-__device__ __forceinline__ uint64_t seed_of(const P& p, int64_t e_global, int32_t k) {
-  return p.base_seed * p.seed_scale + (uint64_t)e_global * p.seed_env_stride + (uint64_t)k * p.seed_episode_stride;
 }
 
 // rng.choice(outcomes, p=probs) = outcomes[searchsorted(cdf, u, side="right")], intended in [0, 4).  The

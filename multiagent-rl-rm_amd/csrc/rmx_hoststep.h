@@ -1,8 +1,10 @@
 // rmx_hoststep.h — the engine's host path: a handle created with cfg.device == RMX_DEVICE_HOST steps its envs on
 // the CPU, over the same compiled tables the gfx950 generic kernels stage into LDS (build_table_blob, rmx_tables.cpp)
-// and with the same rules as their agent_step / env_step (rmx_generic.h).  It serves BASELINE config 1 — the
-// reference's one-env dict API on a CPU (rm_environment_wrapper.py:28-107 under frozen_lake_main.py:336-376) — without
-// a GPU and without a PCIe round trip per call, and every other entry point of include/rmx.h on host buffers.
+// and through the same rules: it instantiates agent_step / env_step / reset_regs / qrm_experiences / mdp_entry of
+// rmx_rules.h, the templates the kernels instantiate, over its own parameter block (HostParams).  It serves BASELINE
+// config 1 — the reference's one-env dict API on a CPU (rm_environment_wrapper.py:28-107 under
+// frozen_lake_main.py:336-376) — without a GPU and without a PCIe round trip per call, and every other entry point of
+// include/rmx.h on host buffers.
 // Plain C++ (no HIP): the sanitizer build (oracle/Makefile `asan`) compiles this file with g++.
 #pragma once
 #include <stdint.h>
@@ -13,42 +15,34 @@
 #include "../../include/rmx.h"
 #include "rmx_host.h"
 #include "rmx_learn.h"
+#include "rmx_rules.h"
 
 namespace rmx {
 
-// numpy's PCG64 (XSL-RR 128/64) state as the device's Pcg (rmx_device.h): 128-bit state and increment
-struct HostPcg {
-  uint64_t hi, lo, ihi, ilo;
-};
-
-struct HostAgent {  // one agent's state while its env is stepped (the device's AgentReg)
-  int32_t x, y, q;
-  uint32_t f;
-  float ret;
-};
-
-struct HostOut {  // one agent-step's outputs (the device's AgentOut)
-  float reward, shaping, renv;
-  bool term, trunc, env_term;
-  uint32_t prev_cell, cell, ev;
+// What the rules of rmx_rules.h read from a parameter block, under the names KParams gives them (rmx_internal.h)
+struct HostParams {
+  int32_t W, HW, A, Q, E, max_t;
+  int64_t N;
+  float hazard_penalty, wall_penalty;
+  int32_t hazard_fail, wall_fail, has_shaping;
+  float reward_modifier;
+  int32_t n_qrm_max, stochastic;
+  int32_t slip_n[4], slip_out[4][4];
+  uint64_t slip_thr[4][4];  // slip_threshold(cdf)
+  uint64_t seed_scale, seed_env_stride, seed_episode_stride;
+  int32_t n_qrm[RMX_MAX_AGENTS], enc_nq[RMX_MAX_AGENTS];
+  int32_t init_q[RMX_MAX_AGENTS], final_q[RMX_MAX_AGENTS], start_x[RMX_MAX_AGENTS], start_y[RMX_MAX_AGENTS];
 };
 
 struct HostEngine {
   rmx_config cfg{};  // scalars (the table pointers are cleared once the tables are copied)
-  // the generic kernels' blob and its section views
+  HostParams p{};    // the rules' view of it
+  // the generic kernels' blob and the view of its sections
   std::vector<unsigned char> blob;
-  const uint16_t* cell = nullptr;
-  const uint8_t* ev = nullptr;
-  const uint8_t* nq = nullptr;
-  const float* rr = nullptr;
-  const float* sh = nullptr;
-  const uint8_t* qrm = nullptr;
+  TableView tv{};
   std::vector<float> disc;           // gamma^t, t = 0 .. max_t + 1
   std::vector<uint16_t> free_cells;  // FrozenLake random starts (x-major non-hole cells)
   std::vector<uint16_t> shuffle;     // the shuffle's working copy of free_cells
-  int32_t init_q[RMX_MAX_AGENTS]{}, final_q[RMX_MAX_AGENTS]{}, start_x[RMX_MAX_AGENTS]{}, start_y[RMX_MAX_AGENTS]{};
-  int32_t n_qrm[RMX_MAX_AGENTS]{}, enc_nq[RMX_MAX_AGENTS]{};
-  uint64_t slip_thr[4][4]{};  // ceil(cdf * 2^53) (slip_threshold, rmx_internal.h's rule)
   bool enc_on = false;        // every agent has an encoder stride: enc_state is computed
   // bound host columns; outputs the caller did not bind go to the engine's own columns (the synchronous calls
   // return them)
@@ -94,10 +88,12 @@ struct HostEngine {
   std::string copy_out(const rmx_buffers& out) const;
 
  private:
-  HostOut agent_step(HostAgent& s, int32_t act, int a, int32_t t1, HostPcg* rng, uint32_t* bad) const;
-  void reset_agents(HostAgent* s, int32_t& t) const;
-  void random_starts(HostPcg& r, HostAgent* s);
-  int32_t slip_choice(int32_t intended, HostPcg& r) const;
+  template <int KIND>
+  uint32_t step_kind(const int32_t* actions, int autoreset, bool hashed, uint64_t seed, int64_t t_global, float* trace,
+                     const LearnCall* lc);
+  template <int KIND>
+  void mdp_kind(int agent, int fix_fl, int32_t* next, float* reward, uint8_t* done) const;
+  void random_starts(Pcg& r, AgentReg* s);
 };
 
 // rmx_learn_rng_seed: default_rng(seeds[i]) of n learners as a generator column [5][n] (state high, state low,

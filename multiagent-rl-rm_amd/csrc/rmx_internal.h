@@ -9,6 +9,7 @@
 #include "../../include/rmx.h"
 #include "rmx_layout.h"
 #include "rmx_learn.h"
+#include "rmx_rules.h"
 
 namespace rmx {
 
@@ -35,20 +36,9 @@ constexpr int kRngSlip = 1, kRngStarts = 2, kRngFixedSeed = 4;
 inline size_t start_cache_rng_off(int A, int64_t N) { return (4 * (size_t)((A + 1) / 2) * (size_t)N + 255) & ~(size_t)255; }
 inline size_t start_cache_bytes(int A, int64_t N) { return start_cache_rng_off(A, N) + 32 * (size_t)N; }
 
-constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
-
-// slip choice threshold (host): Generator.random() = m * 2^-53 with an integer m < 2^53, so cdf <= u exactly when
-// ceil(cdf * 2^53) <= m (the scaling by 2^53 is exact); NaN never compares true, cdf >= 1 never does either
-inline uint64_t slip_threshold(double cdf) {
-  if (!(cdf == cdf)) return ~0ull;
-  if (cdf <= 0.0) return 0ull;
-  if (cdf >= 1.0) return (1ull << 53) + (cdf > 1.0 ? 1ull : 0ull);
-  return (uint64_t)std::ceil(std::ldexp(cdf, 53));
-}
-
 // The slip choice tables of a kernel parameter block (KParams / FastParams) from the config: per intended action the
-// outcome count, the integer thresholds of its cdf and the outcomes, and the shared-cdf fast form when every intended
-// action has the same count and thresholds (the outcomes 0..4 fit 3 bits each).
+// outcome count, the integer thresholds of its cdf (slip_threshold, rmx_rules.h) and the outcomes, and the shared-cdf
+// fast form when every intended action has the same count and thresholds (the outcomes 0..4 fit 3 bits each).
 template <typename P>
 inline void slip_fill(P& p, const rmx_config& c) {
   bool uniform = true;

@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(256) step_kernel(KParams p) {
         p.reward[k] = o[a].reward;
         if (p.shaping) p.shaping[k] = o[a].shaping;
         if (p.renv) p.renv[k] = o[a].renv;
-        if (p.enc_state) p.enc_state[k] = (s[a].y * p.W + s[a].x) * p.enc_nq[a] + s[a].q;
+        if (p.enc_state) p.enc_state[k] = enc_index(s[a], p, a);
         if constexpr (QRM) emit_qrm(o[a], a, e, L, p);
       }
     }
@@ -239,7 +239,7 @@ __global__ void __launch_bounds__(256) rollout_kernel(KParams p, int32_t T, floa
         p.reward[k] = o[a].reward;
         if (p.shaping) p.shaping[k] = o[a].shaping;
         if (p.renv) p.renv[k] = o[a].renv;
-        if (p.enc_state) p.enc_state[k] = (s[a].y * p.W + s[a].x) * p.enc_nq[a] + s[a].q;
+        if (p.enc_state) p.enc_state[k] = enc_index(s[a], p, a);
       }
     }
   }
@@ -324,7 +324,7 @@ __global__ void __launch_bounds__(256) step_kernel_lpe(KParams p) {
     p.reward[k] = o.reward;
     if (p.shaping) p.shaping[k] = o.shaping;
     if (p.renv) p.renv[k] = o.renv;
-    if (p.enc_state) p.enc_state[k] = (s.y * p.W + s.x) * p.enc_nq[a] + s.q;
+    if (p.enc_state) p.enc_state[k] = enc_index(s, p, a);
     if (p.qrm_s) emit_qrm(o, a, e, L, p);
     if (a == 0) {
       p.t[e] = t + 1;
@@ -408,7 +408,7 @@ __global__ void __launch_bounds__(256) rollout_kernel_lpe(KParams p, int32_t T, 
     p.reward[k] = o.reward;
     if (p.shaping) p.shaping[k] = o.shaping;
     if (p.renv) p.renv[k] = o.renv;
-    if (p.enc_state) p.enc_state[k] = (s.y * p.W + s.x) * p.enc_nq[a] + s.q;
+    if (p.enc_state) p.enc_state[k] = enc_index(s, p, a);
     if (a == 0) {
       p.t[e] = t;
       if (p.env_done) p.env_done[e] = (uint8_t)done;
@@ -422,9 +422,7 @@ __global__ void __launch_bounds__(256) rollout_kernel_lpe(KParams p, int32_t T, 
 
 // ------------------------------------------------------------------------------------------------
 // Model construction: RMEnvironmentWrapper.get_mdp (rm_environment_wrapper.py:185-283).  One thread per
-// (encoded state, action) of one agent: decode (x, y, q) with the agent's encoder stride, apply the
-// terminal self-loop rule (is_terminal_state_mdp), else run the same agent_step from timestep 0.
-// done = 255 marks "no entry" (the reference's FrozenLake decode quirk, kept unless fix_fl).
+// (encoded state, action) of one agent; the entry itself is mdp_entry (rmx_rules.h).
 // ------------------------------------------------------------------------------------------------
 template <int KIND>
 __global__ void __launch_bounds__(256) mdp_kernel(KParams p, int ag, int fix_fl, int64_t S, int32_t* __restrict__ next,
@@ -435,45 +433,7 @@ __global__ void __launch_bounds__(256) mdp_kernel(KParams p, int ag, int fix_fl,
   const Lds L = lds_view(lds, p);
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= S * 4) return;
-  const int64_t s = i >> 2;
-  const int a = (int)(i & 3);
-  const int32_t nQ = p.enc_nq[ag];
-  const int32_t q = (int32_t)(s % nQ), pos = (int32_t)(s / nQ);
-  const bool hz = (L.cell[pos] & RMX_CELL_HAZARD) != 0;
-  bool term_state = false;
-  float term_r = 0.0f;
-  if (KIND == RMX_FROZEN_LAKE) {
-    if (hz) {
-      term_state = true;
-      term_r = p.hazard_penalty;
-    } else if (fix_fl && q == p.final_q[ag]) {
-      term_state = true;
-    } else if (!fix_fl) {
-      next[i] = -1;
-      reward[i] = 0.0f;
-      done[i] = 255;
-      return;
-    }
-  } else {
-    if (hz && p.hazard_fail) {
-      term_state = true;
-      term_r = p.hazard_penalty;
-    } else if (q == p.final_q[ag]) {
-      term_state = true;
-    }
-  }
-  if (term_state) {
-    next[i] = (int32_t)s;
-    reward[i] = term_r;
-    done[i] = 1;
-    return;
-  }
-  AgentReg st = {pos % p.W, pos / p.W, q, RMX_F_ACTIVE, 0.0f};
-  uint32_t bad = 0;
-  const AgentOut o = agent_step<KIND>(st, a, ag, 1, L, p, &bad);
-  next[i] = (int32_t)o.cell * nQ + st.q;
-  reward[i] = o.reward;
-  done[i] = (uint8_t)(o.term || o.trunc);
+  mdp_entry<KIND>(i, ag, fix_fl, L, p, next, reward, done);
 }
 
 // ------------------------------------------------------------------------------------------------

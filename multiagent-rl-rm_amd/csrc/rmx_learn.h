@@ -1,6 +1,6 @@
 // rmx_learn.h — the tabular Q-learning / QRM learner's arithmetic and policy, one source for the gfx950 kernel
-// (rmx_learn.hip) and the host path (rmx_hoststep.cpp).  Plain C++: hipcc compiles it for both sides, g++ for the
-// sanitizer build.
+// (rmx_learn.hip) and the host path (rmx_hoststep.cpp).  Plain C++, as rmx_rules.h (whose hash and generator it uses):
+// hipcc compiles it for both sides, g++ for the sanitizer build.
 //
 // Reference semantics restated (paths relative to Alee08/multiagent-rl-rm):
 //   update_q          learning_algorithms/qlearning.py:70-79 (visits += 1 first; lr fixed or 1 / visits;
@@ -17,12 +17,8 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define RMX_LEARN_HD __host__ __device__ __forceinline__
-#else
-#define RMX_LEARN_HD inline
-#endif
+#include "rmx_rules.h"
+
 #if defined(__clang__)
 #define RMX_LEARN_NOFMA _Pragma("clang fp contract(off)")
 #define RMX_LEARN_NOFMA_ATTR
@@ -55,17 +51,8 @@ struct LearnCall {
 };
 enum { kLearnActions = 0, kLearnHash = 1, kLearnNumpy = 2 };  // LearnCall::policy
 
-constexpr uint64_t kLearnGolden = 0x9E3779B97F4A7C15ull;
-
-RMX_LEARN_HD uint64_t learn_splitmix64(uint64_t x) {
-  uint64_t z = x + kLearnGolden;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 // update_q's arithmetic: a = (1 - lr) * cur; b = gamma * maxq; c = r + b; d = lr * c; new = a + d
-RMX_LEARN_NOFMA_ATTR RMX_LEARN_HD double learn_new_q(double cur, double r, double maxq, double gamma, double lr) {
+RMX_LEARN_NOFMA_ATTR RMX_HD double learn_new_q(double cur, double r, double maxq, double gamma, double lr) {
   RMX_LEARN_NOFMA
   const double a = (1.0 - lr) * cur;
   const double b = gamma * maxq;
@@ -75,13 +62,13 @@ RMX_LEARN_NOFMA_ATTR RMX_LEARN_HD double learn_new_q(double cur, double r, doubl
 }
 
 // 1 / visits, correctly rounded
-RMX_LEARN_NOFMA_ATTR RMX_LEARN_HD double learn_rate_of(double visits) {
+RMX_LEARN_NOFMA_ATTR RMX_HD double learn_rate_of(double visits) {
   RMX_LEARN_NOFMA
   return 1.0 / visits;
 }
 
 // r + (gamma * Phi(next) - Phi(prev))
-RMX_LEARN_NOFMA_ATTR RMX_LEARN_HD double learn_shaped(double r, double gamma, double phi_next, double phi_prev) {
+RMX_LEARN_NOFMA_ATTR RMX_HD double learn_shaped(double r, double gamma, double phi_next, double phi_prev) {
   RMX_LEARN_NOFMA
   const double g = gamma * phi_next;
   const double sh = g - phi_prev;
@@ -89,13 +76,13 @@ RMX_LEARN_NOFMA_ATTR RMX_LEARN_HD double learn_shaped(double r, double gamma, do
 }
 
 // Renv + reward_modifier * RQ of the wrapper's reward (rm_environment_wrapper.py:69, 92) in float64
-RMX_LEARN_NOFMA_ATTR RMX_LEARN_HD double learn_reward(float renv, float modifier, float rq) {
+RMX_LEARN_NOFMA_ATTR RMX_HD double learn_reward(float renv, float modifier, float rq) {
   RMX_LEARN_NOFMA
   const double m = (double)modifier * (double)rq;
   return (double)renv + m;
 }
 
-RMX_LEARN_HD double learn_max4(double a, double b, double c, double d) {  // np.max of a row
+RMX_HD double learn_max4(double a, double b, double c, double d) {  // np.max of a row
   double m = a;
   m = b > m ? b : m;
   m = c > m ? c : m;
@@ -105,15 +92,15 @@ RMX_LEARN_HD double learn_max4(double a, double b, double c, double d) {  // np.
 
 // The engine's policy for agent i of global env eg at global step t (include/rmx.h, rmx_learn_step_policy), over the
 // row of the state the step is about to leave.
-RMX_LEARN_HD int32_t learn_policy(uint64_t seed, int64_t t, int64_t n_global, int64_t eg, int A, int i, double epsilon,
+RMX_HD int32_t learn_policy(uint64_t seed, int64_t t, int64_t n_global, int64_t eg, int A, int i, double epsilon,
                                   int best, double r0, double r1, double r2, double r3) {
   const double m = learn_max4(r0, r1, r2, r3);
   if (best) return r0 == m ? 0 : r1 == m ? 1 : r2 == m ? 2 : 3;  // np.argmax: the first maximum
-  const uint64_t ctr = (((uint64_t)t * (uint64_t)n_global + (uint64_t)eg) * (uint64_t)A + (uint64_t)i) * kLearnGolden;
-  const uint64_t h0 = learn_splitmix64(seed ^ ctr);
-  const uint64_t h1 = learn_splitmix64(h0);
+  const uint64_t ctr = (((uint64_t)t * (uint64_t)n_global + (uint64_t)eg) * (uint64_t)A + (uint64_t)i) * kGolden;
+  const uint64_t h0 = splitmix64(seed ^ ctr);
+  const uint64_t h1 = splitmix64(h0);
   if ((double)(h1 >> 11) * 0x1p-53 < epsilon) return (int32_t)(h0 >> 62);
-  const uint64_t h2 = learn_splitmix64(h1);
+  const uint64_t h2 = splitmix64(h1);
   const int e0 = r0 == m, e1 = r1 == m, e2 = r2 == m, e3 = r3 == m;
   const uint64_t n_max = (uint64_t)(e0 + e1 + e2 + e3);
   int pick = (int)(((h2 >> 32) * n_max) >> 32);  // maximum number `pick`, in index order
@@ -129,37 +116,19 @@ RMX_LEARN_HD int32_t learn_policy(uint64_t seed, int64_t t, int64_t n_global, in
 // low half first, the high half buffered in has_uint32 / uinteger; next64 never touches the buffer),
 // _generator.pyx (uniform(0, 1) = next_double; choice of a k-sequence = integers(0, k)) and distributions.c
 // (random_bounded_uint64 -> buffered_bounded_lemire_uint32 for ranges below 2^32; a range of one value draws nothing).
-struct LearnRng {
-  uint64_t hi, lo, ihi, ilo;  // 128-bit state, 128-bit increment
-  uint32_t has, u;            // has_uint32, uinteger
+struct LearnRng : Pcg {  // the generator (rmx_rules.h) and its 32-bit buffer
+  uint32_t has, u;       // has_uint32, uinteger
 };
 
 // The bound column (rmx_learn_rng_bind): uint64 [5][A][N], word w of learner (a, e) at ((w * A + a) * N + e)
-RMX_LEARN_HD uint64_t learn_rng_word4(const LearnRng& r) { return ((uint64_t)r.has << 32) | r.u; }
+RMX_HD uint64_t learn_rng_word4(const LearnRng& r) { return ((uint64_t)r.has << 32) | r.u; }
 
-RMX_LEARN_HD uint64_t learn_pcg_next64(LearnRng& r) {
-  constexpr uint64_t MH = 0x2360ED051FC65DA4ull, ML = 0x4385DF649FCCF645ull;
-  const uint64_t nlo = r.lo * ML;
-#if defined(__HIP_DEVICE_COMPILE__)
-  const uint64_t carry = __umul64hi(r.lo, ML);
-#else
-  const uint64_t carry = (uint64_t)(((unsigned __int128)r.lo * ML) >> 64);
-#endif
-  const uint64_t nhi = carry + r.lo * MH + r.hi * ML;
-  const uint64_t slo = nlo + r.ilo;
-  r.hi = nhi + r.ihi + (slo < nlo ? 1ull : 0ull);
-  r.lo = slo;
-  const uint64_t x = r.hi ^ r.lo;  // XSL-RR of the new state
-  const unsigned rot = (unsigned)(r.hi >> 58);
-  return (x >> rot) | (x << ((64u - rot) & 63u));
-}
-
-RMX_LEARN_HD uint32_t learn_pcg_next32(LearnRng& r) {
+RMX_HD uint32_t learn_pcg_next32(LearnRng& r) {
   if (r.has) {
     r.has = 0;
     return r.u;
   }
-  const uint64_t v = learn_pcg_next64(r);
+  const uint64_t v = pcg_next64(r);
   r.has = 1;
   r.u = (uint32_t)(v >> 32);
   return (uint32_t)v;
@@ -167,7 +136,7 @@ RMX_LEARN_HD uint32_t learn_pcg_next32(LearnRng& r) {
 
 // integers(0, k), 1 <= k < 2^32: Lemire's method on buffered 32-bit draws.  The threshold is 2^32 mod k: 0 for k = 2
 // and 4, so of a row's tie counts only k = 3 can redraw, and only on a zero low half.
-RMX_LEARN_HD uint32_t learn_bounded(LearnRng& r, uint32_t k) {
+RMX_HD uint32_t learn_bounded(LearnRng& r, uint32_t k) {
   if (k == 1u) return 0u;
   uint64_t m = (uint64_t)learn_pcg_next32(r) * k;
   uint32_t left = (uint32_t)m;
@@ -184,8 +153,8 @@ RMX_LEARN_HD uint32_t learn_bounded(LearnRng& r, uint32_t k) {
 // choose_action on the learner's own generator (include/rmx.h, RMX_LEARN_NUMPY), over the row of the state the step is
 // about to leave.  The explore draw is taken whatever epsilon is; a row with no entry equal to its maximum (a NaN
 // maximum, where the reference raises) gives action 3 without a further draw.
-RMX_LEARN_HD int32_t learn_policy_numpy(LearnRng& r, double epsilon, double r0, double r1, double r2, double r3) {
-  const double d = (double)(learn_pcg_next64(r) >> 11) * 0x1p-53;
+RMX_HD int32_t learn_policy_numpy(LearnRng& r, double epsilon, double r0, double r1, double r2, double r3) {
+  const double d = (double)(pcg_next64(r) >> 11) * 0x1p-53;
   if (d < epsilon) return (int32_t)learn_bounded(r, 4u);
   const double m = learn_max4(r0, r1, r2, r3);
   const int e0 = r0 == m, e1 = r1 == m, e2 = r2 == m, e3 = r3 == m;
@@ -199,7 +168,7 @@ RMX_LEARN_HD int32_t learn_policy_numpy(LearnRng& r, double epsilon, double r0, 
 }
 
 // One 32-B table row: two 16-B loads on the device (the maximum is taken in registers, by whoever uses the row)
-RMX_LEARN_HD void learn_load_row(const double* row, double (&out)[4]) {
+RMX_HD void learn_load_row(const double* row, double (&out)[4]) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const double2* r2 = reinterpret_cast<const double2*>(row);
   const double2 lo = r2[0], hi = r2[1];
@@ -209,7 +178,7 @@ RMX_LEARN_HD void learn_load_row(const double* row, double (&out)[4]) {
 #endif
 }
 
-// One agent-step's outcome as the learner reads it (the kernels' AgentOut / the host's HostOut, and the RM state
+// One agent-step's outcome as the learner reads it (AgentOut, rmx_rules.h, and the RM state
 // before and after the step).
 struct LearnStep {
   uint32_t prev_cell, cell, ev;
@@ -239,8 +208,8 @@ struct LearnExp {
   double r;
   bool done;
 };
-RMX_LEARN_HD int learn_n_exp(const LearnParams& lp, const LearnTables& T) { return lp.use_qrm ? T.n_qrm : 1; }
-RMX_LEARN_HD bool learn_experience(const LearnParams& lp, const LearnTables& T, const LearnStep& o, int j, int64_t S,
+RMX_HD int learn_n_exp(const LearnParams& lp, const LearnTables& T) { return lp.use_qrm ? T.n_qrm : 1; }
+RMX_HD bool learn_experience(const LearnParams& lp, const LearnTables& T, const LearnStep& o, int j, int64_t S,
                                    LearnExp& x) {
   const int32_t nQ = T.enc_nq;
   if (lp.use_qrm) {
@@ -268,7 +237,7 @@ RMX_LEARN_HD bool learn_experience(const LearnParams& lp, const LearnTables& T, 
 
 // update_q (qlearning.py:70-79) of one experience on learner table qa / va ([S_max][4], one (agent, env)): three
 // independent loads (the entry, its visit count, the next state's row unless done), then the two stores
-RMX_LEARN_HD void learn_update_q(const LearnParams& lp, double* qa, double* va, const LearnExp& x, int k) {
+RMX_HD void learn_update_q(const LearnParams& lp, double* qa, double* va, const LearnExp& x, int k) {
   const int64_t i = x.s * 4 + k;
   const double cur = qa[i];
   double lr = lp.lr;
@@ -287,7 +256,7 @@ RMX_LEARN_HD void learn_update_q(const LearnParams& lp, double* qa, double* va, 
 }
 
 // Every experience of one agent-step, strictly in order on the one table.  k: the action's table column (0..3).
-RMX_LEARN_HD void learn_agent(const LearnParams& lp, const LearnTables& T, const LearnStep& o, double* qa, double* va,
+RMX_HD void learn_agent(const LearnParams& lp, const LearnTables& T, const LearnStep& o, double* qa, double* va,
                               int k, int64_t S) {
   const int n = learn_n_exp(lp, T);
   for (int j = 0; j < n; ++j) {

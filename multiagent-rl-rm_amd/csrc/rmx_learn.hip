@@ -1,7 +1,7 @@
 // rmx_learn.hip — the learn step for gfx950: auto-reset, optional action choice, the wrapper step and the tabular
 // Q-learning / QRM update of every (env, agent) learner in ONE launch (include/rmx.h, rmx_learn_step*).
 //
-// One thread owns one environment, as in step_kernel (rmx_kernels.hip), and runs env_step of rmx_generic.h over its A
+// One thread owns one environment, as in step_kernel (rmx_kernels.hip), and runs env_step of rmx_rules.h over its A
 // agents in registers: the step rules stay in one place, and the env-level rule (episode end) needs no cross-lane
 // work.  The thread then walks its agents' experiences, one agent after the other (learn_agent, rmx_learn.h): the
 // counterfactuals are formed from AgentOut and the LDS-staged RM tables and consumed on the spot; they are never
@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
               const int64_t plane = (int64_t)p.A * N;
               uint64_t* w = lc.rng + (int64_t)a * N + e;
               const uint64_t w4 = w[4 * plane];
-              LearnRng r = {w[0], w[plane], w[2 * plane], w[3 * plane], (uint32_t)(w4 >> 32), (uint32_t)w4};
+              LearnRng r = {{w[0], w[plane], w[2 * plane], w[3 * plane]}, (uint32_t)(w4 >> 32), (uint32_t)w4};
               act[a] = learn_policy_numpy(r, lc.epsilon, lo.x, lo.y, hi.x, hi.y);
               w[0] = r.hi;
               w[plane] = r.lo;
@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
         p.reward[k] = o[a].reward;
         if (p.shaping) p.shaping[k] = o[a].shaping;
         if (p.renv) p.renv[k] = o[a].renv;
-        if (p.enc_state) p.enc_state[k] = (s[a].y * p.W + s[a].x) * p.enc_nq[a] + s[a].q;
+        if (p.enc_state) p.enc_state[k] = enc_index(s[a], p, a);
         if (p.qrm_s) emit_qrm(o[a], a, e, L, p);
       }
     }

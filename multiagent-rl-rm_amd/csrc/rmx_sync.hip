@@ -6,8 +6,8 @@
 // launch, a completion signal and one or more copies every step.  Here one workgroup stays resident between
 // calls instead: the env's state lives in its registers, the tables in its LDS, and a lane polls a request
 // line in pinned host memory.  The host writes the actions and bumps the request number; the workgroup steps
-// (the same agent_step / env_step as the generic kernels, rmx_generic.h), writes the output columns straight
-// into host memory, fences at system scope and bumps the acknowledgement number, which the host polls in
+// (the same agent_step / env_step as the generic kernels and the host path, rmx_rules.h), writes the output columns
+// straight into host memory, fences at system scope and bumps the acknowledgement number, which the host polls in
 // its own memory.  Each side only reads memory local to it in its poll loop.
 //
 // Lifetime: the workgroup exits on an exit request, after idle_ticks without a request (the host relaunches on
@@ -26,11 +26,6 @@ namespace rmx {
 namespace {
 
 constexpr uint32_t kSyncTimeout = 0;
-
-// The seed-schedule seed of env e_global in its k-th episode under base seed `base` (rmx.h, stochastic mode).
-__device__ __forceinline__ uint64_t schedule_seed(const KParams& p, uint64_t base, int64_t e_global, int32_t k) {
-  return base * p.seed_scale + (uint64_t)e_global * p.seed_env_stride + (uint64_t)k * p.seed_episode_stride;
-}
 
 // The outputs of one request into the host-mapped mailbox (SyncCols' packed records): 16-B buffer stores with
 // sc0 | sc1 (system scope, write-through to host memory); the caller waits for their completion (s_waitcnt)
@@ -51,7 +46,7 @@ __device__ __forceinline__ void store_outputs(const SyncCols& c, const KParams& 
   for (int a = 0; a < AMAX; ++a) {
     if (AMAX <= 4 || a < p.A) {
       const uint32_t off = ((uint32_t)e * (uint32_t)A + (uint32_t)a) * 32u;
-      const uint32_t enc = (uint32_t)((s[a].y * p.W + s[a].x) * p.enc_nq[a] + s[a].q);
+      const uint32_t enc = (uint32_t)enc_index(s[a], p, a);
       __builtin_amdgcn_raw_buffer_store_b128(
           u32x4{((uint32_t)s[a].x & 0xFFFFu) | ((uint32_t)s[a].y << 16), (uint32_t)s[a].q, s[a].f,
                 stepped ? __float_as_uint(o[a].reward) : 0u},
@@ -242,7 +237,7 @@ __global__ void __launch_bounds__(256) resident_kernel(KParams p, SyncIO io) {
     if (p.enc_state)
 #pragma unroll
       for (int a = 0; a < AMAX; ++a)
-        if (AMAX <= 4 || a < p.A) p.enc_state[(int64_t)a * N + e] = (s[a].y * p.W + s[a].x) * p.enc_nq[a] + s[a].q;
+        if (AMAX <= 4 || a < p.A) p.enc_state[(int64_t)a * N + e] = enc_index(s[a], p, a);
   }
   if (__any(bad_any) && (threadIdx.x & 63) == 0) atomicOr(p.err, 1u);
   wave_flush(p.slab, ls, __any(ls.episodes != 0));

@@ -58,7 +58,7 @@ HASHED_SOURCES = ("rmx_kernels.hip", "rmx_fast.hip", "rmx_fast_step.inc", "rmx_s
                   "rmx_handle.h", "rmx_capi_create.cpp", "rmx_capi_sync.cpp", "rmx_capi_seq.cpp", "rmx_capi_learn.cpp", "rmx_capi_state.cpp",
                   "rmx_comd.cpp", "rmx_build_info.cpp", "rmx_internal.h", "rmx_layout.h", "rmx_host.h", "rmx_device.h",
                   "rmx_generic.h", "rmx_comd.h", "rmx_hoststep.cpp", "rmx_hoststep.h", "rmx_learn.hip", "rmx_learn.h",
-                  "../../include/rmx.h",
+                  "rmx_rules.h", "../../include/rmx.h",
                   "Makefile")
 
 
