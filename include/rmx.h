@@ -53,6 +53,7 @@ extern "C" {
 #define RMX_E_HIP (-2)      /* HIP runtime error                 -> RuntimeError          */
 #define RMX_E_ACTION (-3)   /* an action outside [0,4] was seen  -> ValueError            */
 #define RMX_E_STATE (-4)    /* buffers not bound / wrong sizes   -> RuntimeError          */
+#define RMX_E_TRACE (-5)    /* a Q(lambda) trace list was full   -> RuntimeError          */
 
 #define RMX_DEVICE_HOST (-1) /* rmx_config.device: the host path (no GPU) */
 
@@ -470,6 +471,59 @@ int rmx_learn_step_policy(rmx_handle* h, double epsilon, int flags, uint64_t see
 /* the learners' numpy generators for RMX_LEARN_NUMPY: bind the caller's column [5][A][N] (NULL unbinds), seed it */
 int rmx_learn_rng_bind(rmx_handle* h, uint64_t* rng);
 int rmx_learn_rng_seed(rmx_handle* h, const uint64_t* seeds_host /* [A][N] */, void* hip_stream);
+
+/* ---- Watkins Q(lambda) learners fused into the step ------------------------------------------------------------
+ * QLearningLambda.update (learning_algorithms/qlearning_lambda.py:33-84) behind AgentRL.update_policy (multi_agent/
+ * agent_rl.py:117-192), one learner per (agent a, env e) on the tables rmx_learn_bind bound (q filled with the
+ * reference's zeros by the caller; visits optional unless learning_rate == 0).  rmx_learn_lambda_bind, after
+ * rmx_learn_bind, turns the handle's learners into Q(lambda) ones: rmx_learn_step and rmx_learn_step_policy then run
+ * the Q(lambda) learn step, still ONE launch, with the same three policies (choose_action is QLearning's, line for
+ * line), the same dynamics (RMX_LEARN_DYN_ENV included) and the same columns and statistics.
+ * The experience is the non-QRM one of the Q-learning section: s, sn, done (trunc_is_terminal as there) and
+ * r = (double)Renv + (double)reward_modifier*(double)RQ; there is no QRM and no shaping (update ignores info), so a
+ * learner bound with use_qrm or use_rsh is refused.  update_policy never passes next_action: update then takes the
+ * argmax as the next action, which is always greedy, so under the reference's call path the traces always decay and
+ * are never cut.  That path is what is reproduced; an explicit next_action is not served.
+ * One update, i = s*4 + k, each step one IEEE float64 operation, never fused:
+ *   visits[i] += 1; lr = learning_rate, or 1/visits[i] (correctly rounded) when learning_rate == 0;
+ *   best = 0 when done, else max(q[sn][0..3]), read before any write of this update;
+ *   td = (r + gamma*best) - q[i];  e[i] = 1 (replacing traces);  c = lr*td;  q[j] = q[j] + (c*e[j]) for every j;
+ *   done: every trace of the learner becomes 0;  else g = gamma*lambd and e[j] = e[j]*g for every j.
+ * The reference's e_table is dense and its update sweeps the whole table.  The engine keeps, per learner, the list
+ * of its live traces, caller-owned like q and visits:
+ *   trace_idx int32 [A][L][N], trace_val float64 [A][L][N], trace_cnt int32 [A][N] (the caller zeroes trace_cnt),
+ *   slot-major: slot j of learner (a, e) at [(a*L + j)*N + e];  slots 0..cnt-1 hold distinct cells i, each with a
+ *   trace that is not 0: a cell is listed iff its dense e would be non-zero.  A trace that decays to exactly 0
+ *   (through the subnormals) leaves the list; order is kept.
+ * Bit-exactness: adding c*0.0 leaves a float64 unchanged for every finite c and every value but -0.0 (-0.0 + 0.0 is
+ * +0.0), so q, visits and the dense e rebuilt from the lists equal the reference's bit for bit, under the conditions
+ * of the Q-learning section, for every initial q value but -0.0 (the reference starts at zeros) and while c stays
+ * finite (an infinite or NaN c turns the reference's whole table to NaN).
+ * Capacity: L = rmx_learn_lambda_slots() = 4*S_max can never overflow.  A caller may bind a smaller cap; under
+ * auto-resetting learn steps a list never exceeds max_t + 1 entries.  A trace that finds its list full: the cell's own
+ * update is applied, the trace is not kept, and the error word gets a bit that rmx_check_errors reports as
+ * RMX_E_TRACE (an invalid action reported at the same time wins).  Nothing is ever written at or past slot cap.
+ * When the lists are emptied: a learn step empties an env's lists when it auto-resets that env (env.reset() clears
+ * every agent's traces whatever ended the episode, ma_frozen_lake.py:77-81, ma_office.py:100-102; an OfficeWorld
+ * truncation passes terminated = False: the update decays, the reset wipes), before the policy reads its rows, with or
+ * without RMX_LEARN_UPDATE; rmx_reset (the masked envs), rmx_reset_sync and rmx_set_state empty them on a handle with
+ * Q(lambda) bound; rmx_learn_traces_clear(h, env_mask_dev, stream) empties those of the masked envs (NULL: all; a host
+ * handle takes host bytes) in stream order.  rmx_step / rmx_step_hashed / rmx_step_report / rmx_step_seq /
+ * rmx_rollout and the synchronous steps leave the lists alone, their auto-resets included: a caller who mixes them in
+ * calls rmx_learn_traces_clear.  A step without RMX_LEARN_UPDATE touches no list but for the wipe above; nor does an
+ * action without a table column, nor an experience whose s or sn is outside the agent's rows.
+ * reset() does not call learn_done_episode on a QLearningLambda, so epsilon stays fixed.  Not reproduced: an explicit
+ * next_action, softmax action selection, epsilon decay.  The arrays are not part of rmx_get_state.
+ * rmx_learn_lambda_bind: a NULL idx unbinds (Q-learning again); a later rmx_learn_bind drops the binding.  A device
+ * handle takes device pointers, a host handle host pointers; the extents (A*cap*N, A*cap*N, A*N) cannot be checked.
+ * RMX_E_INVALID with a message, before any device work: lambd not finite or outside [0, 1], cap < 1 or cap > 4*S_max,
+ * a NULL val / cnt or an array not aligned to its element type (4, 8 and 4 bytes), a learner bound with use_qrm or
+ * use_rsh.  RMX_E_STATE: before rmx_learn_bind (rmx_learn_traces_clear: before
+ * rmx_learn_lambda_bind). */
+int rmx_learn_lambda_slots(const rmx_handle* h, int32_t* l_full);
+int rmx_learn_lambda_bind(rmx_handle* h, double lambd, int32_t cap, int32_t* trace_idx, double* trace_val,
+                          int32_t* trace_cnt);
+int rmx_learn_traces_clear(rmx_handle* h, const uint8_t* env_mask_dev, void* hip_stream);
 
 /* Synchronise and report kernel-side errors (e.g. RMX_E_ACTION), then clear them. */
 int rmx_check_errors(rmx_handle* h);

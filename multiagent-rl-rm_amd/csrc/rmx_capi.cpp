@@ -410,7 +410,7 @@ int rmx_reset(rmx_handle* h, const uint8_t* env_mask_dev, uint64_t seed, void* s
   HIP_TRY(rmx::launch_reset(p, env_mask_dev, 1, as_stream(stream)), "reset launch");
   HIP_TRY(invalidate_next_shuffles(h, as_stream(stream)), "reset precompute");
   h->rs_stale = false;
-  return RMX_OK;
+  return lambda_clear(h, env_mask_dev, stream);  // env.reset() clears every learner's traces (Q(lambda) bound)
 }
 
 int rmx_step(rmx_handle* h, const int32_t* actions_dev, int autoreset, void* stream) {
@@ -612,12 +612,17 @@ int rmx_step_info(const rmx_handle* h, int64_t* out, int32_t n) {
   return RMX_OK;
 }
 
+static const char kTraceFullMsg[] =
+    "a Q(lambda) trace found its list full (rmx_learn_lambda_bind cap): the cell was updated, its trace not kept";
+
 int rmx_check_errors(rmx_handle* h) {
   if (!h) return fail(RMX_E_INVALID, "handle is NULL");
   if (h->host) {
     const uint32_t err = h->host->err;
     h->host->err = 0;
-    return err ? fail(RMX_E_ACTION, "an action outside [0,4] was stepped (treated as wait)") : RMX_OK;
+    if (err & 1u) return fail(RMX_E_ACTION, "an action outside [0,4] was stepped (treated as wait)");
+    if (err & rmx::kErrTraceFull) return fail(RMX_E_TRACE, kTraceFullMsg);
+    return RMX_OK;
   }
   SYNC_END_OR_RETURN(h);
   HIP_TRY(hipSetDevice(h->device), "hipSetDevice");
@@ -626,6 +631,7 @@ int rmx_check_errors(rmx_handle* h) {
   HIP_TRY(hipMemcpy(&err, h->d_err, sizeof(err), hipMemcpyDeviceToHost), "err copy");
   HIP_TRY(hipMemset(h->d_err, 0, sizeof(uint32_t)), "err clear");
   if (err & 1u) return fail(RMX_E_ACTION, "an action outside [0,4] was stepped (treated as wait)");
+  if (err & rmx::kErrTraceFull) return fail(RMX_E_TRACE, kTraceFullMsg);
   return RMX_OK;
 }
 

@@ -1,7 +1,8 @@
 // rmx_capi_learn.cpp — the tabular Q-learning / QRM learner fused into the step (rmx_learn.h, rmx_learn.hip): the
-// rmx_learn_* entry points.  Owns rmx_handle::learn.
+// rmx_learn_* entry points, the Q(lambda) binding and its trace lists included.  Owns rmx_handle::learn.
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <exception>
 #include <vector>
 
@@ -19,7 +20,7 @@ static int do_learn_step(rmx_handle* h, const int32_t* actions, rmx::LearnCall l
     lc.rng = h->host ? h->host->learn_rng : h->learn.rng;
     if (!lc.rng) return fail(RMX_E_STATE, "RMX_LEARN_NUMPY needs a generator column (rmx_learn_rng_bind)");
   }
-  if (h->host) {
+  if (h->host) {  // (a full trace list: HostEngine::err, as the device's error word)
     h->host->step(actions, autoreset, false, seed, t_global, nullptr, &lc);
     return RMX_OK;
   }
@@ -32,7 +33,17 @@ static int do_learn_step(rmx_handle* h, const int32_t* actions, rmx::LearnCall l
   p.autoreset = autoreset ? 1 : 0;
   // slip / random starts (a learner bound with RMX_LEARN_DYN_ENV): the kernel reads and writes the env generator and
   // episode columns rmx_bind required, and none of the fast path's caches (the reset cache, the next-episode shuffles)
-  HIP_TRY(rmx::launch_learn_step(p, h->learn.params, lc, h->cfg.kind, h->tables_bytes, as_stream(stream)), "learn step launch");
+  HIP_TRY(rmx::launch_learn_step(p, h->learn.params, lc, h->learn.lam_on ? &h->learn.lam : nullptr, h->cfg.kind,
+                                 h->tables_bytes, as_stream(stream)),
+          "learn step launch");
+  return RMX_OK;
+}
+
+int rmx::capi::lambda_clear(rmx_handle* h, const uint8_t* env_mask_dev, void* stream) {
+  if (!h->learn.lam_on) return RMX_OK;
+  HIP_TRY(hipSetDevice(h->device), "hipSetDevice");
+  HIP_TRY(rmx::launch_traces_clear(h->learn.lam.cnt, env_mask_dev, h->cfg.n_agents, h->cfg.n_envs, as_stream(stream)),
+          "trace clear launch");
   return RMX_OK;
 }
 
@@ -88,6 +99,7 @@ int rmx_learn_bind(rmx_handle* h, const rmx_learn_config* lc, double* q, double*
     lp.phi = lc->use_rsh ? h->host->learn_phi.data() : nullptr;
     h->host->learn = lp;
     h->host->learn_on = true;
+    h->host->lam_on = false;  // a new learner: Q-learning until rmx_learn_lambda_bind
     return RMX_OK;
   }
   if ((reinterpret_cast<uintptr_t>(q) & 15u) || (reinterpret_cast<uintptr_t>(visits) & 15u))
@@ -101,6 +113,7 @@ int rmx_learn_bind(rmx_handle* h, const rmx_learn_config* lc, double* q, double*
   }
   h->learn.params = lp;
   h->learn.on = true;
+  h->learn.lam_on = false;  // a new learner: Q-learning until rmx_learn_lambda_bind
   return RMX_OK;
 }
 
@@ -142,6 +155,61 @@ int rmx_learn_rng_seed(rmx_handle* h, const uint64_t* seeds, void* stream) {
           "generator column upload");
   HIP_TRY(hipStreamSynchronize(as_stream(stream)), "generator column upload");
   return RMX_OK;
+}
+
+int rmx_learn_lambda_slots(const rmx_handle* h, int32_t* l_full) {
+  if (!h || !l_full) return fail(RMX_E_INVALID, "handle or l_full is NULL");
+  int64_t s_max = 0;
+  const int rc = rmx_learn_states(h, &s_max);
+  if (rc) return rc;
+  if (s_max * 4 > INT32_MAX) return fail(RMX_E_INVALID, "4 * S_max exceeds the int32 cell indices of the trace lists");
+  *l_full = (int32_t)(s_max * 4);
+  return RMX_OK;
+}
+
+int rmx_learn_lambda_bind(rmx_handle* h, double lambd, int32_t cap, int32_t* idx, double* val, int32_t* cnt) {
+  if (!h) return fail(RMX_E_INVALID, "handle is NULL");
+  if (!(h->host ? h->host->learn_on : h->learn.on))
+    return fail(RMX_E_STATE, "no learner bound (rmx_learn_bind comes before rmx_learn_lambda_bind)");
+  if (!idx) {  // back to Q-learning
+    if (h->host)
+      h->host->lam_on = false;
+    else
+      h->learn.lam_on = false;
+    return RMX_OK;
+  }
+  const rmx::LearnParams& lp = h->host ? h->host->learn : h->learn.params;
+  if (lp.use_qrm || lp.use_rsh)
+    return fail(RMX_E_INVALID, "Q(lambda) has no QRM and no shaping (the learner was bound with use_qrm / use_rsh)");
+  if (!std::isfinite(lambd) || lambd < 0.0 || lambd > 1.0) return fail(RMX_E_INVALID, "lambd must be in [0, 1]");
+  int32_t l_full = 0;
+  const int rc = rmx_learn_lambda_slots(h, &l_full);
+  if (rc) return rc;
+  if (cap < 1 || cap > l_full) return fail(RMX_E_INVALID, "cap must be in [1, 4 * S_max] (rmx_learn_lambda_slots)");
+  if (!val || !cnt) return fail(RMX_E_INVALID, "trace_val or trace_cnt is NULL");
+  if ((reinterpret_cast<uintptr_t>(idx) & 3u) || (reinterpret_cast<uintptr_t>(val) & 7u) ||
+      (reinterpret_cast<uintptr_t>(cnt) & 3u))
+    return fail(RMX_E_INVALID, "the trace arrays must be aligned to their element types");
+  const rmx::LambdaParams lam = {lambd, idx, val, cnt, cap};
+  if (h->host) {
+    h->host->lam = lam;
+    h->host->lam_on = true;
+  } else {
+    h->learn.lam = lam;
+    h->learn.lam_on = true;
+  }
+  return RMX_OK;
+}
+
+int rmx_learn_traces_clear(rmx_handle* h, const uint8_t* env_mask_dev, void* stream) {
+  if (!h) return fail(RMX_E_INVALID, "handle is NULL");
+  if (!(h->host ? h->host->lam_on : h->learn.lam_on))
+    return fail(RMX_E_STATE, "no Q(lambda) trace lists bound (rmx_learn_lambda_bind)");
+  if (h->host) {
+    h->host->traces_clear(env_mask_dev);
+    return RMX_OK;
+  }
+  return lambda_clear(h, env_mask_dev, stream);
 }
 
 int rmx_learn_step(rmx_handle* h, const int32_t* actions, int autoreset, void* stream) {

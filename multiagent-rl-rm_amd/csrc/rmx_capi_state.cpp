@@ -145,6 +145,7 @@ int rmx_set_state(rmx_handle* h, const void* host_blob, size_t bytes) {
     }
     h->base_seed = h->host->base_seed = hd.base_seed;
     std::memcpy(h->host->stats, hd.stats, sizeof(hd.stats));
+    h->host->traces_clear(nullptr);  // the Q(lambda) lists are not in the blob: the restored envs start without traces
     return RMX_OK;
   }
   SYNC_END_OR_RETURN(h);
@@ -162,6 +163,8 @@ int rmx_set_state(rmx_handle* h, const void* host_blob, size_t bytes) {
   if (h->d_es) HIP_TRY(hipMemset(h->d_es, 0, h->es_bytes), "stats clear");
   HIP_TRY(hipMemcpy(h->d_slab, hd.stats, sizeof(hd.stats), hipMemcpyHostToDevice), "stats restore");
   HIP_TRY(refresh_starts(h, nullptr), "restore start cache / precompute");  // the restored base seed's
+  // the Q(lambda) lists are not in the blob: the restored envs start without traces
+  if ((rc = lambda_clear(h, nullptr, nullptr))) return rc;
   HIP_TRY(hipDeviceSynchronize(), "sync after set_state");
   return RMX_OK;
 }

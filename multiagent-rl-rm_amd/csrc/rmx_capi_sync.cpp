@@ -275,6 +275,7 @@ int rmx_reset_sync(rmx_handle* h, uint64_t seed, const rmx_buffers* out_host, vo
   // on the caller's stream would not be ordered before a launch on another stream
   h->rs_stale = h->d_rsc || h->d_nx;
   if ((rc = sync_request(h, rmx::kSyncReset, 0, seed, nullptr, stream))) return rc;
+  if ((rc = lambda_clear(h, nullptr, stream))) return rc;  // env.reset() clears every learner's traces
   return sync_copy_out(h, out_host);
 }
 

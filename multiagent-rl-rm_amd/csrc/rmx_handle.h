@@ -131,6 +131,9 @@ struct rmx_handle {
     bool on = false;
     double* d_phi = nullptr;
     uint64_t* rng = nullptr;  // rmx_learn_rng_bind: the learners' numpy generators, caller's [5][A][N]
+    // rmx_learn_lambda_bind: the learners are Q(lambda) ones over the caller's trace lists (lam_on)
+    rmx::LambdaParams lam{};
+    bool lam_on = false;
   } learn;
 };
 
@@ -202,6 +205,10 @@ int do_step(rmx_handle* h, const int32_t* actions, int hashed, uint64_t seed, in
             void* stream);
 bool report_fuses(const rmx_handle* h);
 rmx::FastParams report_fp(const rmx_handle* h, const int32_t* actions, int autoreset, double* stats_out);
+
+// rmx_capi_learn.cpp.  Empty the Q(lambda) trace lists of the masked envs (NULL: every env) in stream order; nothing
+// on a handle without Q(lambda) bound.  A host handle's lists are emptied by HostEngine::reset itself.
+int lambda_clear(rmx_handle* h, const uint8_t* env_mask_dev, void* stream);
 
 // rmx_capi_sync.cpp.  End the resident workgroup (if any): the device columns are current afterwards.
 int sync_end(rmx_handle* h);

@@ -188,6 +188,16 @@ void HostEngine::reset(const uint8_t* mask, uint64_t seed) {
       buf.ep_ret[k] = s[a].ret;
     }
   }
+  traces_clear(mask);  // env.reset() clears every learner's traces
+}
+
+void HostEngine::traces_clear(const uint8_t* mask) {
+  if (!lam_on) return;
+  const int64_t N = cfg.n_envs;
+  for (int64_t e = 0; e < N; ++e) {
+    if (mask && !mask[e]) continue;
+    for (int a = 0; a < cfg.n_agents; ++a) lam.cnt[(int64_t)a * N + e] = 0;
+  }
 }
 
 uint32_t HostEngine::step(const int32_t* actions, int autoreset, bool hashed, uint64_t seed, int64_t t_global,
@@ -226,6 +236,8 @@ uint32_t HostEngine::step_kind(const int32_t* actions, int autoreset, bool hashe
     if (rng_on) rng = {buf.rng[e], buf.rng[N + e], buf.rng[2 * N + e], buf.rng[3 * N + e]};
     if (autoreset && (s[0].f & RMX_F_ENV_DONE)) {  // the loop's reset() before this step
       reset_regs(s, t, p);
+      if (lc && lam_on)  // a learn step's reset clears the traces of every agent's learner
+        for (int a = 0; a < A; ++a) lam.cnt[(int64_t)a * N + e] = 0;
       if (rng_on) {  // env.rng = default_rng(seed of the next episode)
         const int32_t k = buf.episode[e] + 1;
         buf.episode[e] = k;
@@ -302,12 +314,18 @@ uint32_t HostEngine::step_kind(const int32_t* actions, int autoreset, bool hashe
         const LearnStep st = {o[a].prev_cell, o[a].cell, o[a].ev,   q_pre[a],  s[a].q,
                               o[a].env_term,  o[a].term, o[a].trunc, o[a].renv};
         const int64_t base = ((int64_t)a * N + e) * learn.s_max * 4;
-        learn_agent(learn, T, st, learn.q + base, learn.visits ? learn.visits + base : nullptr, act[a], mdp_states(a));
+        double* va = learn.visits ? learn.visits + base : nullptr;
+        if (lam_on)
+          bad |= learn_lambda_agent(learn, lam, T, st, learn.q + base, va, act[a], mdp_states(a), a, N, e)
+                     ? (uint32_t)kErrTraceFull
+                     : 0u;
+        else
+          learn_agent(learn, T, st, learn.q + base, va, act[a], mdp_states(a));
       }
     }
   }
   err |= bad;
-  return bad;
+  return bad & 1u;  // (a full trace list is reported by rmx_check_errors only)
 }
 
 void HostEngine::fill_actions(uint64_t seed, int64_t t0, int32_t T, int32_t* out) const {

@@ -58,7 +58,7 @@ struct HostEngine {
   int32_t* enc = nullptr;
   uint64_t base_seed = 123;
   double stats[RMX_NSTATS]{};
-  uint32_t err = 0;       // an invalid action was stepped (rmx_check_errors)
+  uint32_t err = 0;       // bit 0: an invalid action was stepped; kErrTraceFull: a full trace list (rmx_check_errors)
   bool pending = false;   // rmx_step_sync_begin ran a step whose outputs rmx_sync_wait has not returned
   uint32_t pending_bad = 0;
   bool last_reset = false;  // the synchronous call before the copy was a reset (no step outputs)
@@ -67,6 +67,11 @@ struct HostEngine {
   bool learn_on = false;
   std::vector<double> learn_phi;
   uint64_t* learn_rng = nullptr;  // rmx_learn_rng_bind: the learners' numpy generators, caller's [5][A][N]
+  // rmx_learn_lambda_bind: Q(lambda) learners over the caller's trace lists (host pointers)
+  LambdaParams lam{};
+  bool lam_on = false;
+  // cnt[a][e] = 0 for the masked envs (NULL: every env); nothing without Q(lambda) bound
+  void traces_clear(const uint8_t* mask);
 
   // "" or the reason the config cannot run on the host path (after validate_config)
   std::string init(const rmx_config& c);
@@ -77,7 +82,7 @@ struct HostEngine {
   // action outside [0, 4] (or "wait" under FrozenLake slip) was stepped (as wait)
   // lc != NULL: a learn step (rmx_learn_step / rmx_learn_step_policy): the policy's actions when lc->policy (seed,
   // t_global are then the policy hash's; lc->policy == kLearnNumpy: the learners' own generators in lc->rng), the
-  // bound learner's update when lc->update
+  // bound learner's update when lc->update (lam_on: the Q(lambda) sweep, and the lists emptied on auto-reset)
   uint32_t step(const int32_t* actions, int autoreset, bool hashed = false, uint64_t seed = 0, int64_t t_global = 0,
                 float* trace = nullptr, const LearnCall* lc = nullptr);
   void fill_actions(uint64_t seed, int64_t t0, int32_t T, int32_t* out) const;

@@ -368,8 +368,11 @@ hipError_t launch_fill_actions(uint64_t seed, int64_t t0, int32_t T, int64_t n_g
 hipError_t launch_mdp(const KParams& p, int kind, int ag, int fix_fl, int64_t S, int32_t* next, float* reward,
                       uint8_t* done, size_t lds, hipStream_t st);
 // the learn step (rmx_learn.hip): the thread-per-env step over the generic tables plus every learner's update
-hipError_t launch_learn_step(const KParams& p, const LearnParams& lp, const LearnCall& lc, int kind, size_t lds,
-                             hipStream_t st);
+// lam != NULL: the Q(lambda) learn step over the bound trace lists (one launch, like the other)
+hipError_t launch_learn_step(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
+                             int kind, size_t lds, hipStream_t st);
+// cnt[a][e] = 0 for every env of the device mask (NULL: every env)
+hipError_t launch_traces_clear(int32_t* cnt, const uint8_t* mask, int A, int64_t N, hipStream_t st);
 constexpr int kStatsPartials = 512;  // max blocks of each partial pass of the stats reduction
 constexpr int kStatsEnvsPerThread = 4;  // per-env slots summed by each thread of the stats launch
 // sums the per-wave slab and, if es_ret != NULL, the per-env slots of the fast path (FastParams: one row [N]

@@ -265,4 +265,140 @@ RMX_HD void learn_agent(const LearnParams& lp, const LearnTables& T, const Learn
   }
 }
 
+// ---- Watkins Q(lambda) with replacing traces: QLearningLambda.update (learning_algorithms/qlearning_lambda.py:33-84)
+// behind AgentRL.update_policy, which never passes next_action: the next action is then the argmax, always greedy, so
+// the traces always decay and are never cut (include/rmx.h, "Watkins Q(lambda) learners").
+// The reference's e_table is dense and every update sweeps the whole table; here each learner keeps the list of its
+// live traces.  Adding c * 0.0 leaves a float64 unchanged for every finite c and every value but -0.0, so the list
+// gives the dense update's tables bit for bit.
+// The lists bound by rmx_learn_lambda_bind, slot-major: slot j of learner (a, e) at (a * cap + j) * N + e, so that with
+// one thread per env a wave's read of slot j is one contiguous run.  Invariant: slots 0 .. cnt - 1 hold distinct cell
+// indices i = s * 4 + k, each with a trace that is not 0: a cell is listed iff its dense e would be non-zero.
+struct LambdaParams {
+  double lambd;
+  int32_t* idx;  // [A][cap][N]
+  double* val;   // [A][cap][N]
+  int32_t* cnt;  // [A][N]
+  int32_t cap;
+};
+
+// How many list slots one sweep step has in flight.  The read-modify-writes of one list hit distinct cells, so a batch
+// is B independent gathers (a wave: 64 * B lines) and B independent scatters, not a chain of dependent round trips.
+// Four keeps the kernel's registers where the eight-agent bucket can still hold its agents; the lists of this workload
+// are a few tens of entries long, so deeper batches would mostly run empty.
+enum { kLambdaBatch = 4 };
+// the bit of the handle's error word a full list raises (bit 0: an invalid action); rmx_check_errors: RMX_E_TRACE
+enum : uint32_t { kErrTraceFull = 2u };
+
+// c = lr * td, td = (r + gamma * best) - cur: three operations, then the scalar product numpy forms first
+RMX_LEARN_NOFMA_ATTR RMX_HD double learn_lambda_c(double cur, double r, double best, double gamma, double lr) {
+  RMX_LEARN_NOFMA
+  const double b = gamma * best;
+  const double t = r + b;
+  const double td = t - cur;
+  return lr * td;
+}
+
+// q + (c * e)
+RMX_LEARN_NOFMA_ATTR RMX_HD double learn_lambda_add(double q, double c, double e) {
+  RMX_LEARN_NOFMA
+  const double d = c * e;
+  return q + d;
+}
+
+RMX_LEARN_NOFMA_ATTR RMX_HD double learn_lambda_mul(double a, double b) {
+  RMX_LEARN_NOFMA
+  return a * b;
+}
+
+// One update of learner table qa / va over its list (ti / tv: slot 0 of the learner, `stride` elements between slots;
+// *tc its length).  Returns true when the cell's trace found the list full: the cell's own update is applied, the trace
+// is not kept, and nothing is written at or past slot cap.
+RMX_HD bool learn_lambda_update(const LearnParams& lp, double lambd, int32_t cap, double* qa, double* va,
+                                const LearnExp& x, int k, int32_t* ti, double* tv, int64_t stride, int32_t* tc) {
+  const int64_t i = x.s * 4 + k;
+  // 1. the entry, its visit count, the next state's row: read before any write of this update
+  const double cur = qa[i];
+  double lr = lp.lr;
+  if (va) {
+    const double v = va[i] + 1.0;
+    va[i] = v;
+    if (lr == 0.0) lr = learn_rate_of(v);
+  }
+  double best = 0.0;
+  if (!x.done) {
+    double row[4];
+    learn_load_row(qa + x.sn * 4, row);
+    best = learn_max4(row[0], row[1], row[2], row[3]);
+  }
+  // 2. c and g
+  const double c = learn_lambda_c(cur, x.r, best, lp.gamma, lr);
+  const double g = learn_lambda_mul(lp.gamma, lambd);
+  // 3.-6. one sweep, kLambdaBatch slots at a time: the slot of cell i takes 1.0 first, every slot adds c * val to its
+  // cell, and unless done the decayed traces that are not 0 are written back compacted, in order (slot w <= j: a
+  // write never lands on a slot still to be read)
+  const int32_t n = *tc < cap ? (*tc > 0 ? *tc : 0) : cap;  // (a count the caller did not zero reads no slot past cap)
+  int32_t w = 0;
+  bool found = false;
+  for (int32_t j0 = 0; j0 < n; j0 += kLambdaBatch) {
+    int32_t ci[kLambdaBatch];
+    double cv[kLambdaBatch], cq[kLambdaBatch];
+    RMX_UNROLL
+    for (int b = 0; b < kLambdaBatch; ++b)
+      if (j0 + b < n) {
+        ci[b] = ti[(int64_t)(j0 + b) * stride];
+        cv[b] = tv[(int64_t)(j0 + b) * stride];
+      }
+    RMX_UNROLL
+    for (int b = 0; b < kLambdaBatch; ++b)
+      if (j0 + b < n) cq[b] = qa[ci[b]];
+    RMX_UNROLL
+    for (int b = 0; b < kLambdaBatch; ++b)
+      if (j0 + b < n) {
+        if (ci[b] == (int32_t)i) {
+          cv[b] = 1.0;
+          found = true;
+        }
+        qa[ci[b]] = learn_lambda_add(cq[b], c, cv[b]);
+        if (!x.done) {
+          const double d = learn_lambda_mul(cv[b], g);
+          if (d != 0.0) {  // a trace that reached exactly 0 is dropped
+            ti[(int64_t)w * stride] = ci[b];
+            tv[(int64_t)w * stride] = d;
+            ++w;
+          }
+        }
+      }
+  }
+  // 7. a cell that was not listed: its own update with trace 1.0, and the decayed trace appended
+  bool full = false;
+  if (!found) {
+    qa[i] = learn_lambda_add(cur, c, 1.0);
+    if (!x.done && g != 0.0) {
+      if (w < cap) {
+        ti[(int64_t)w * stride] = (int32_t)i;
+        tv[(int64_t)w * stride] = g;
+        ++w;
+      } else {
+        full = true;
+      }
+    }
+  }
+  // 8. terminated: every trace of this learner becomes 0
+  *tc = x.done ? 0 : w;
+  return full;
+}
+
+// The one experience of an agent-step under Q(lambda) (no QRM, no shaping: update ignores info).  k: the action's
+// table column.  An experience outside the agent's rows touches neither the tables nor the list.
+RMX_HD bool learn_lambda_agent(const LearnParams& lp, const LambdaParams& lam, const LearnTables& T,
+                               const LearnStep& o, double* qa, double* va, int k, int64_t S, int a, int64_t N,
+                               int64_t e) {
+  LearnExp x;
+  if (!learn_experience(lp, T, o, 0, S, x)) return false;
+  const int64_t slot0 = (int64_t)a * lam.cap * N + e;
+  return learn_lambda_update(lp, lam.lambd, lam.cap, qa, va, x, k, lam.idx + slot0, lam.val + slot0, N,
+                             lam.cnt + (int64_t)a * N + e);
+}
+
 }  // namespace rmx

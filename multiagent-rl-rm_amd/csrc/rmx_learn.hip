@@ -18,8 +18,12 @@
 // from the seed schedule and draws the random starts before the policy reads its rows, the step draws the slips from
 // it, and the four words are stored after the step.  The learners' draws all come before the first slip draw and the
 // two kinds of generator never mix.  Tail lanes touch neither column.
+// With LAMBDA (rmx_learn_lambda_bind: Watkins Q(lambda) learners) the update is learn_lambda_agent's sweep over the
+// learner's own list of live traces (rmx_learn.h; slot-major [A][cap][N], so a wave's read of slot j is contiguous), in
+// batches of independent read-modify-writes, and the auto-reset empties the env's lists before the policy reads its
+// rows.  Tail lanes and the agents past A touch no list.
 //
-// Reference semantics: rmx_learn.h (update, experiences, policy), rmx_kernels.hip (the step).
+// Reference semantics: rmx_learn.h (update, experiences, policy, the Q(lambda) sweep), rmx_kernels.hip (the step).
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -34,8 +38,15 @@ namespace rmx {
 // POLICY: kLearnActions (the caller's actions), kLearnHash (the engine's hash policy) or kLearnNumpy (each learner's
 // numpy generator, read from and written back to lc.rng); everything the third adds sits behind if constexpr.
 // STOCH: the env's own generator (slip, the per-episode reseed, random starts), likewise behind if constexpr.
-template <int KIND, int AMAX, int POLICY, bool STOCH>
-__global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams lp, LearnCall lc) {
+// LAMBDA: the Q(lambda) learners (rmx_learn_lambda_bind): the auto-reset empties the env's trace lists and the update
+// is learn_lambda_agent's sweep over the learner's list; behind if constexpr, as the other two.
+// LAM is the one LambdaParams argument of the LAMBDA kernels and empty for the others, whose signature (and code) is
+// that of the kernel without Q(lambda).
+__device__ __forceinline__ const LambdaParams& lambda_of(const LambdaParams& lam) { return lam; }
+
+template <int KIND, int AMAX, int POLICY, bool STOCH, bool LAMBDA, typename... LAM>
+__global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams lp, LearnCall lc, LAM... lam_arg) {
+  static_assert(sizeof...(LAM) == (LAMBDA ? 1 : 0), "LAMBDA kernels take the LambdaParams, the others nothing");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int64_t N = p.N;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -67,12 +78,19 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
   LaneStats ls = {0.0, 0, 0, 0};
   bool done = false;
   uint32_t bad = 0;
+  bool full = false;  // LAMBDA: a trace found its list full
   AgentOut o[AMAX];
   if (live) {
     Pcg rng = {0, 0, 0, 0};
     if constexpr (STOCH) rng = {p.rng[e], p.rng[N + e], p.rng[2 * N + e], p.rng[3 * N + e]};
     if (p.autoreset && (s[0].f & RMX_F_ENV_DONE)) {
       reset_regs<AMAX>(s, t, p);
+      if constexpr (LAMBDA) {  // env.reset() clears the traces of every agent's learner (ma_frozen_lake.py:77-81)
+        const LambdaParams& lam = lambda_of(lam_arg...);
+#pragma unroll
+        for (int a = 0; a < AMAX; ++a)
+          if (AMAX <= 4 || a < p.A) lam.cnt[(int64_t)a * N + e] = 0;
+      }
       if constexpr (STOCH) {  // env.rng = default_rng(seed of the next episode)
         const int32_t k = p.episode[e] + 1;
         p.episode[e] = k;
@@ -164,8 +182,13 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
           const LearnStep st = {o[a].prev_cell, o[a].cell, o[a].ev,     q_pre[a],
                                 s[a].q,         o[a].env_term, o[a].term, o[a].trunc, o[a].renv};
           const int64_t base = ((int64_t)a * N + e) * lp.s_max * 4;
-          learn_agent(lp, T, st, lp.q + base, lp.visits ? lp.visits + base : nullptr, act[a],
-                      (int64_t)p.HW * p.enc_nq[a]);
+          if constexpr (LAMBDA)
+            full |= learn_lambda_agent(lp, lambda_of(lam_arg...), T, st, lp.q + base,
+                                       lp.visits ? lp.visits + base : nullptr, act[a], (int64_t)p.HW * p.enc_nq[a], a,
+                                       N, e);
+          else
+            learn_agent(lp, T, st, lp.q + base, lp.visits ? lp.visits + base : nullptr, act[a],
+                        (int64_t)p.HW * p.enc_nq[a]);
         }
       }
     }
@@ -173,44 +196,74 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
   if (__any(bad)) {
     if ((threadIdx.x & 63) == 0) atomicOr(p.err, 1u);
   }
+  if constexpr (LAMBDA) {
+    if (__any(full)) {
+      if ((threadIdx.x & 63) == 0) atomicOr(p.err, kErrTraceFull);
+    }
+  }
   wave_flush_slot(p.slab, slot, ls, __any(done));
 }
 
 template <int KIND, int AMAX, bool STOCH>
-static hipError_t launch_learn_t(const KParams& p, const LearnParams& lp, const LearnCall& lc, dim3 g, dim3 b,
-                                 size_t lds, hipStream_t st) {
+static hipError_t launch_learn_t(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
+                                 dim3 g, dim3 b, size_t lds, hipStream_t st) {
+  if (lam) {
+    if (lc.policy == kLearnNumpy)
+      hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnNumpy, STOCH, true, LambdaParams>), g, b, lds, st, p, lp, lc,
+                         *lam);
+    else if (lc.policy)
+      hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnHash, STOCH, true, LambdaParams>), g, b, lds, st, p, lp, lc,
+                         *lam);
+    else
+      hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnActions, STOCH, true, LambdaParams>), g, b, lds, st, p, lp, lc,
+                         *lam);
+    return hipGetLastError();
+  }
   if (lc.policy == kLearnNumpy)
-    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnNumpy, STOCH>), g, b, lds, st, p, lp, lc);
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnNumpy, STOCH, false>), g, b, lds, st, p, lp, lc);
   else if (lc.policy)
-    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnHash, STOCH>), g, b, lds, st, p, lp, lc);
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnHash, STOCH, false>), g, b, lds, st, p, lp, lc);
   else
-    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnActions, STOCH>), g, b, lds, st, p, lp, lc);
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnActions, STOCH, false>), g, b, lds, st, p, lp, lc);
   return hipGetLastError();
 }
 
 template <int KIND, bool STOCH>
-static hipError_t launch_learn_k(const KParams& p, const LearnParams& lp, const LearnCall& lc, dim3 g, dim3 b,
-                                 size_t lds, hipStream_t st) {
+static hipError_t launch_learn_k(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
+                                 dim3 g, dim3 b, size_t lds, hipStream_t st) {
   switch (amax_bucket(p.A)) {
-    case 1: return launch_learn_t<KIND, 1, STOCH>(p, lp, lc, g, b, lds, st);
-    case 2: return launch_learn_t<KIND, 2, STOCH>(p, lp, lc, g, b, lds, st);
-    case 3: return launch_learn_t<KIND, 3, STOCH>(p, lp, lc, g, b, lds, st);
-    case 4: return launch_learn_t<KIND, 4, STOCH>(p, lp, lc, g, b, lds, st);
-    default: return launch_learn_t<KIND, 8, STOCH>(p, lp, lc, g, b, lds, st);
+    case 1: return launch_learn_t<KIND, 1, STOCH>(p, lp, lc, lam, g, b, lds, st);
+    case 2: return launch_learn_t<KIND, 2, STOCH>(p, lp, lc, lam, g, b, lds, st);
+    case 3: return launch_learn_t<KIND, 3, STOCH>(p, lp, lc, lam, g, b, lds, st);
+    case 4: return launch_learn_t<KIND, 4, STOCH>(p, lp, lc, lam, g, b, lds, st);
+    default: return launch_learn_t<KIND, 8, STOCH>(p, lp, lc, lam, g, b, lds, st);
   }
 }
 
 // 256-thread blocks, one thread per env (the per-wave statistics slab is sized for that geometry at rmx_create).
 // p.rng_on (the handle has slip or random starts; the caller has checked the learner's dynamics and the rng / episode
 // columns) selects the STOCH instantiations; every other handle runs the kernels it always ran.
-hipError_t launch_learn_step(const KParams& p, const LearnParams& lp, const LearnCall& lc, int kind, size_t lds,
-                             hipStream_t st) {
+// lam != NULL: the Q(lambda) kernels.
+hipError_t launch_learn_step(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
+                             int kind, size_t lds, hipStream_t st) {
   const dim3 g((unsigned)((p.N + 255) / 256)), b(256);
   if (p.rng_on)
-    return kind == RMX_FROZEN_LAKE ? launch_learn_k<RMX_FROZEN_LAKE, true>(p, lp, lc, g, b, lds, st)
-                                   : launch_learn_k<RMX_OFFICE_WORLD, true>(p, lp, lc, g, b, lds, st);
-  return kind == RMX_FROZEN_LAKE ? launch_learn_k<RMX_FROZEN_LAKE, false>(p, lp, lc, g, b, lds, st)
-                                 : launch_learn_k<RMX_OFFICE_WORLD, false>(p, lp, lc, g, b, lds, st);
+    return kind == RMX_FROZEN_LAKE ? launch_learn_k<RMX_FROZEN_LAKE, true>(p, lp, lc, lam, g, b, lds, st)
+                                   : launch_learn_k<RMX_OFFICE_WORLD, true>(p, lp, lc, lam, g, b, lds, st);
+  return kind == RMX_FROZEN_LAKE ? launch_learn_k<RMX_FROZEN_LAKE, false>(p, lp, lc, lam, g, b, lds, st)
+                                 : launch_learn_k<RMX_OFFICE_WORLD, false>(p, lp, lc, lam, g, b, lds, st);
+}
+
+// rmx_learn_traces_clear and the resets of a handle with Q(lambda) bound: cnt[a][e] = 0 for the masked envs
+__global__ void __launch_bounds__(256) traces_clear_kernel(int32_t* cnt, const uint8_t* mask, int A, int64_t N) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= N || (mask && !mask[e])) return;
+  for (int a = 0; a < A; ++a) cnt[(int64_t)a * N + e] = 0;
+}
+
+hipError_t launch_traces_clear(int32_t* cnt, const uint8_t* mask, int A, int64_t N, hipStream_t st) {
+  hipLaunchKernelGGL(traces_clear_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, cnt, mask, A, N);
+  return hipGetLastError();
 }
 
 }  // namespace rmx

@@ -8,7 +8,8 @@ hand-written HIP kernels for gfx950 behind the C ABI of ``include/rmx.h``.
 * ``rmx.tables``  — host table compiler (maps, walls, RM indices, final state, shaping potentials)
 * ``rmx.engine``  — ``VecRMEnv``: batched device engine over the C ABI (torch tensors as buffers)
 * ``rmx.compat``  — reference-shaped dict API (``RMEnvironmentWrapper``-style reset/step)
-* ``rmx.learn``   — ``VecQLearning``: one tabular Q-learning / QRM learner per (env, agent), updated inside the step
+* ``rmx.learn``   — ``VecQLearning``: one tabular Q-learning / QRM learner per (env, agent), updated inside the step;
+                    ``VecQLambda``: the same with Watkins Q(lambda) learners over sparse trace lists
 * ``rmx.dist``    — one-process-per-GPU env sharding + RCCL all-reduce of episode statistics
 """
 __version__ = "0.1.0"
@@ -26,4 +27,7 @@ def __getattr__(name):  # lazy: the engine needs torch + the HIP library, the ta
     if name == "VecQLearning":
         from .learn import VecQLearning
         return VecQLearning
+    if name == "VecQLambda":
+        from .learn import VecQLambda
+        return VecQLambda
     raise AttributeError(name)

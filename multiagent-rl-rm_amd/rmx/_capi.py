@@ -14,7 +14,7 @@ from .tables import CompiledTables
 LIB_NAME = "librmx.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
-RMX_OK, RMX_E_INVALID, RMX_E_HIP, RMX_E_ACTION, RMX_E_STATE = 0, -1, -2, -3, -4
+RMX_OK, RMX_E_INVALID, RMX_E_HIP, RMX_E_ACTION, RMX_E_STATE, RMX_E_TRACE = 0, -1, -2, -3, -4, -5
 F_ACTIVE, F_FAIL, F_TERM, F_TRUNC, F_ENV_TERM, F_RM_TERM, F_ENV_DONE = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
 F_STEPS_SHIFT = 16
 NSTATS = 4
@@ -29,7 +29,8 @@ EXPORTS = (
     "rmx_step_sync_begin", "rmx_sync_wait", "rmx_sync_end", "rmx_step_seq", "rmx_queue_counters", "rmx_queue_info",
     "rmx_code_object_check", "rmx_device_count", "rmx_queue_timing", "rmx_queue_times", "rmx_step_info",
     "rmx_seq_packed", "rmx_learn_states", "rmx_learn_bind", "rmx_learn_step", "rmx_learn_step_policy",
-    "rmx_learn_rng_bind", "rmx_learn_rng_seed",
+    "rmx_learn_rng_bind", "rmx_learn_rng_seed", "rmx_learn_lambda_slots", "rmx_learn_lambda_bind",
+    "rmx_learn_traces_clear",
 )
 LEARN_UPDATE, LEARN_BEST, LEARN_NUMPY = 1, 2, 4  # RMX_LEARN_*
 LEARN_DYN_FIXED, LEARN_DYN_ENV = 0, 1  # rmx_learn_config.dynamics
@@ -237,6 +238,9 @@ def load_library(path: str = None, check_source: bool = True):
         "rmx_learn_step_policy": (C.c_int, [vp, C.c_double, C.c_int, u64, i64, C.c_int, vp, vp]),
         "rmx_learn_rng_bind": (C.c_int, [vp, vp]),
         "rmx_learn_rng_seed": (C.c_int, [vp, vp, vp]),
+        "rmx_learn_lambda_slots": (C.c_int, [vp, C.POINTER(C.c_int32)]),
+        "rmx_learn_lambda_bind": (C.c_int, [vp, C.c_double, i32, vp, vp, vp]),
+        "rmx_learn_traces_clear": (C.c_int, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -12,6 +12,9 @@ random-start scenario a learn step reseeds the env's generator at every auto-res
 the actions from the fresh start's rows, draws the slips and updates with the intended action and the state actually
 reached, in the runner's order; the env's generator and the learners' own never mix.  Whole reference training runs
 on such worlds are reproduced bit for bit, the env's generator and episode count included (tests/golden/slearn_*.npz).
+
+``VecQLambda`` is the same for the reference's ``QLearningLambda`` (Watkins Q(lambda), replacing traces): the learn step
+then sweeps each learner's list of live traces instead of the reference's dense ``e_table`` (tests/golden/lambda_*.npz).
 """
 from __future__ import annotations
 
@@ -183,3 +186,88 @@ class VecQLearning:
         three = t.full_like(s, 3)
         return t.where(rows[..., 0] == m, three - 3,
                        t.where(rows[..., 1] == m, three - 2, t.where(rows[..., 2] == m, three - 1, three)))
+
+
+class VecQLambda(VecQLearning):
+    """One Watkins Q(lambda) learner with replacing traces per (env, agent): the reference's ``QLearningLambda``
+    (learning_algorithms/qlearning_lambda.py) as ``AgentRL.update_policy`` drives it, i.e. without ``next_action``:
+    the traces always decay and are wiped when an update is terminal or the env resets (include/rmx.h, "Watkins
+    Q(lambda) learners").  ``step``, ``act_step``, ``greedy`` and the generator accessors are ``VecQLearning``'s; the
+    learn step behind them is the Q(lambda) one, still one launch on a GPU env.
+
+    The reference's dense ``e_table`` is kept as per-learner lists of the live traces: ``trace_idx`` /  ``trace_val``
+    ``[A, L, N]`` (slot-major) and ``trace_cnt`` ``[A, N]``; ``traces()`` rebuilds the dense table.  ``trace_cap``
+    (default: ``4 * S_max``, which cannot overflow) is L; a trace that finds its list full is dropped and
+    ``env.check_errors()`` raises ``RuntimeError``.  Steps taken through the env's own ``step`` / ``step_seq`` /
+    ``rollout`` leave the lists alone, their auto-resets included: call ``clear_traces`` when mixing them in.
+    Not reproduced: an explicit ``next_action``, softmax action selection, epsilon decay."""
+
+    def __init__(self, env, gamma, lambd, learning_rate=None, qtable_init=0.0, trunc_is_terminal=None,
+                 policy_seeds=None, trace_cap=None):
+        super().__init__(env, gamma, learning_rate, qtable_init=qtable_init, use_qrm=False, use_rsh=False,
+                         trunc_is_terminal=trunc_is_terminal, policy_seeds=policy_seeds)
+        full = C.c_int32()
+        _capi.check(self.lib.rmx_learn_lambda_slots(env._h, C.byref(full)), "rmx_learn_lambda_slots")
+        self.trace_full = int(full.value)
+        self.trace_cap = self.trace_full if trace_cap is None else int(trace_cap)
+        self.lambd = float(lambd)
+        cap = max(self.trace_cap, 1)  # (a refused cap is refused by the bind below, not by the allocation)
+        if self.host:
+            self.trace_idx = np.zeros((env.A, cap, env.N), np.int32)
+            self.trace_val = np.zeros((env.A, cap, env.N), np.float64)
+            self.trace_cnt = np.zeros((env.A, env.N), np.int32)
+        else:
+            t = env.torch
+            self.trace_idx = t.zeros((env.A, cap, env.N), dtype=t.int32, device=env.device)
+            self.trace_val = t.zeros((env.A, cap, env.N), dtype=t.float64, device=env.device)
+            self.trace_cnt = t.zeros((env.A, env.N), dtype=t.int32, device=env.device)
+        self.bind_traces(self.trace_idx, self.trace_val, self.trace_cnt, self.trace_cap)
+
+    def _ptr(self, x):
+        return x.ctypes.data if self.host else x.data_ptr()
+
+    def bind_traces(self, idx, val, cnt, cap, lambd=None):
+        """rmx_learn_lambda_bind with the caller's own arrays (numpy on a host env, tensors or views on a GPU env)."""
+        _capi.check(self.lib.rmx_learn_lambda_bind(self.env._h, self.lambd if lambd is None else float(lambd),
+                                                   int(cap), self._ptr(idx), self._ptr(val), self._ptr(cnt)),
+                    "rmx_learn_lambda_bind")
+        self.trace_idx, self.trace_val, self.trace_cnt, self.trace_cap = idx, val, cnt, int(cap)
+
+    def unbind_traces(self):
+        """Back to plain Q-learning steps on the same tables (``bind_traces`` binds the lists again)."""
+        _capi.check(self.lib.rmx_learn_lambda_bind(self.env._h, 0.0, 0, None, None, None), "rmx_learn_lambda_bind")
+
+    def trace_counts(self):
+        """The length of every learner's list: [A, N] int32 (numpy)."""
+        if self.host:
+            return self.trace_cnt.copy()
+        self.env.sync_end()
+        return self.trace_cnt.cpu().numpy()
+
+    def traces(self):
+        """The dense ``e_table`` of every learner rebuilt from its list: [A, N, S_max, 4] float64 (numpy)."""
+        cnt = self.trace_counts()
+        idx = self.trace_idx if self.host else self.trace_idx.cpu().numpy()
+        val = self.trace_val if self.host else self.trace_val.cpu().numpy()
+        A, N = cnt.shape
+        e = np.zeros((A, N, self.S_max * 4), np.float64)
+        for j in range(int(cnt.max(initial=0))):
+            a, n = np.nonzero(cnt > j)
+            e[a, n, idx[a, j, n]] = val[a, j, n]
+        return e.reshape(A, N, self.S_max, 4)
+
+    def clear_traces(self, mask=None):
+        """Empty the lists of the masked envs ([N] bool / uint8; None: every env)."""
+        env = self.env
+        p = None
+        if mask is not None:
+            if self.host:
+                m = np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
+                p = m.ctypes.data
+            else:
+                m = env.torch.as_tensor(mask).to(device=env.device, dtype=env.torch.uint8).contiguous()
+                p = m.data_ptr()
+            if (m.size if self.host else m.numel()) != env.N:
+                raise ValueError(f"mask must be [N={env.N}]")
+        # (a device mask is read in stream order, as env.reset's)
+        _capi.check(self.lib.rmx_learn_traces_clear(env._h, p, self._stream()), "rmx_learn_traces_clear")
