@@ -449,8 +449,26 @@ int rmx_step_info(const rmx_handle* h, int64_t* out, int32_t n);
  * work: a NULL handle / config / q, gamma or learning_rate not finite or negative, no enc_nq, use_qrm with
  * n_qrm_max == 0, use_rsh without use_qrm or phi, 1/visits without visits, a dynamics value other than the two below,
  * cfg.stochastic / cfg.random_starts under RMX_LEARN_DYN_FIXED, epsilon outside [0, 1], unknown flags.  A learn step before rmx_bind or rmx_learn_bind: RMX_E_STATE.
- * Not served: rmx_step_seq windows (learn steps are stream launches), the dict API, the tables in rmx_get_state
- * (they are the caller's). */
+ * Not served: rmx_step_seq windows (learn steps are stream launches; T of them in one launch: rmx_learn_run below),
+ * the dict API, the tables in rmx_get_state (they are the caller's).
+ * Runs (rmx_learn_run): exactly T consecutive calls of rmx_learn_step_policy(h, epsilon, flags, seed, t_global + k,
+ * autoreset = 1, actions_out ? actions_out + k*A*N : NULL, stream), k = 0..T-1, in ONE launch on a device handle
+ * (one thread per env runs its T steps; state, t, the env generator and the episode count stay in registers and the
+ * columns are stored once at the end).  The same three flags, whatever learner is bound (Q-learning or QRM, with or
+ * without rsh and visits, Q(lambda) while rmx_learn_lambda_bind is active) and the learner's dynamics
+ * (RMX_LEARN_DYN_ENV: slip, the per-episode reseed, random starts, the episode column).  Auto-reset is always on, as
+ * in rmx_rollout; a run on the caller's own actions (rmx_learn_step's mode) is not served.  After the call everything
+ * is as the T single steps leave it, bit for bit: every state column, the output columns (the LAST step's reward,
+ * renv, shaping, env_done, enc_state and QRM columns), q and visits, the learners' generator column (words 0, 1 and
+ * 4; the increment is never written), the env generator and episode columns, the trace lists and counts, and the
+ * error word (the same RMX_E_TRACE when a bound cap overflows).  Episode statistics: the integer ones (episodes,
+ * successes, sum of lengths) are equal; a device handle sums the returns per lane over the run and then per wave, so
+ * the return sum is associated differently from T single steps and agrees to rounding (as rmx_rollout against
+ * rmx_step).  A host handle runs the T steps one after the other: everything is equal there, the return sum too.
+ * RMX_E_INVALID: T < 1 or T > RMX_LEARN_RUN_MAX (one launch stays bounded: at the slowest measured learn step 4096
+ * steps are a few seconds), epsilon outside [0, 1], unknown flags.  RMX_E_STATE: before rmx_bind or rmx_learn_bind,
+ * RMX_LEARN_NUMPY with no column bound.  Each with a message, before any device work.  Like every other entry point
+ * the call ends a resident synchronous workgroup first. */
 typedef struct rmx_learn_config {
   double gamma, learning_rate /* 0: 1/visits */;
   int32_t use_qrm, use_rsh, trunc_is_terminal, dynamics /* RMX_LEARN_DYN_* */;
@@ -468,6 +486,10 @@ int rmx_learn_step(rmx_handle* h, const int32_t* actions, int autoreset, void* h
 /* the policy's actions (written to actions_out [A][N] unless NULL), the step, and with RMX_LEARN_UPDATE the update */
 int rmx_learn_step_policy(rmx_handle* h, double epsilon, int flags, uint64_t seed, int64_t t_global, int autoreset,
                           int32_t* actions_out, void* hip_stream);
+/* T auto-reset policy steps (1 <= T <= RMX_LEARN_RUN_MAX) in one launch; actions_out [T][A][N] or NULL */
+#define RMX_LEARN_RUN_MAX 4096
+int rmx_learn_run(rmx_handle* h, int32_t T, double epsilon, int flags, uint64_t seed, int64_t t_global,
+                  int32_t* actions_out /* [T][A][N] or NULL */, void* hip_stream);
 /* the learners' numpy generators for RMX_LEARN_NUMPY: bind the caller's column [5][A][N] (NULL unbinds), seed it */
 int rmx_learn_rng_bind(rmx_handle* h, uint64_t* rng);
 int rmx_learn_rng_seed(rmx_handle* h, const uint64_t* seeds_host /* [A][N] */, void* hip_stream);

@@ -232,4 +232,43 @@ int rmx_learn_step_policy(rmx_handle* h, double epsilon, int flags, uint64_t see
   return do_learn_step(h, nullptr, lc, seed, t_global, autoreset, stream);
 }
 
+int rmx_learn_run(rmx_handle* h, int32_t T, double epsilon, int flags, uint64_t seed, int64_t t_global,
+                  int32_t* actions_out, void* stream) {
+  if (!h) return fail(RMX_E_INVALID, "handle is NULL");
+  if (T < 1 || T > RMX_LEARN_RUN_MAX) return fail(RMX_E_INVALID, "T must be in [1, RMX_LEARN_RUN_MAX]");
+  if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(RMX_E_INVALID, "epsilon must be in [0, 1]");
+  if (flags & ~(RMX_LEARN_UPDATE | RMX_LEARN_BEST | RMX_LEARN_NUMPY)) return fail(RMX_E_INVALID, "unknown learn step flags");
+  if (!h->bound) return fail(RMX_E_STATE, "buffers not bound (rmx_bind)");
+  if (!(h->host ? h->host->learn_on : h->learn.on)) return fail(RMX_E_STATE, "no learner bound (rmx_learn_bind)");
+  rmx::LearnCall lc{};
+  lc.epsilon = epsilon;
+  lc.policy = (flags & RMX_LEARN_NUMPY) ? rmx::kLearnNumpy : rmx::kLearnHash;
+  lc.update = (flags & RMX_LEARN_UPDATE) ? 1 : 0;
+  lc.best = (flags & RMX_LEARN_BEST) ? 1 : 0;
+  lc.actions_out = actions_out;
+  if (lc.policy == rmx::kLearnNumpy) {
+    lc.rng = h->host ? h->host->learn_rng : h->learn.rng;
+    if (!lc.rng) return fail(RMX_E_STATE, "RMX_LEARN_NUMPY needs a generator column (rmx_learn_rng_bind)");
+  }
+  if (h->host) {  // the same T steps, one after the other
+    const int64_t AN = (int64_t)h->cfg.n_agents * h->cfg.n_envs;
+    for (int32_t k = 0; k < T; ++k) {
+      h->host->step(nullptr, 1, false, seed, t_global + k, nullptr, &lc);
+      if (lc.actions_out) lc.actions_out += AN;
+    }
+    return RMX_OK;
+  }
+  SYNC_END_OR_RETURN(h);
+  HIP_TRY(hipSetDevice(h->device), "hipSetDevice");
+  rmx::KParams p = base_params(h);
+  p.actions = nullptr;
+  p.seed = seed;
+  p.t_global = t_global;
+  p.autoreset = 1;
+  HIP_TRY(rmx::launch_learn_run(p, h->learn.params, lc, h->learn.lam_on ? &h->learn.lam : nullptr, T, h->cfg.kind,
+                                h->tables_bytes, as_stream(stream)),
+          "learn run launch");
+  return RMX_OK;
+}
+
 }  // extern "C"

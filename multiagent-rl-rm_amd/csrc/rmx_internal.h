@@ -371,6 +371,9 @@ hipError_t launch_mdp(const KParams& p, int kind, int ag, int fix_fl, int64_t S,
 // lam != NULL: the Q(lambda) learn step over the bound trace lists (one launch, like the other)
 hipError_t launch_learn_step(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
                              int kind, size_t lds, hipStream_t st);
+// T consecutive auto-reset learn steps with the engine's or the learners' own policy in one launch (rmx_learn_run.hip)
+hipError_t launch_learn_run(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
+                            int32_t T, int kind, size_t lds, hipStream_t st);
 // cnt[a][e] = 0 for every env of the device mask (NULL: every env)
 hipError_t launch_traces_clear(int32_t* cnt, const uint8_t* mask, int A, int64_t N, hipStream_t st);
 constexpr int kStatsPartials = 512;  // max blocks of each partial pass of the stats reduction

@@ -30,10 +30,11 @@ EXPORTS = (
     "rmx_code_object_check", "rmx_device_count", "rmx_queue_timing", "rmx_queue_times", "rmx_step_info",
     "rmx_seq_packed", "rmx_learn_states", "rmx_learn_bind", "rmx_learn_step", "rmx_learn_step_policy",
     "rmx_learn_rng_bind", "rmx_learn_rng_seed", "rmx_learn_lambda_slots", "rmx_learn_lambda_bind",
-    "rmx_learn_traces_clear",
+    "rmx_learn_traces_clear", "rmx_learn_run",
 )
 LEARN_UPDATE, LEARN_BEST, LEARN_NUMPY = 1, 2, 4  # RMX_LEARN_*
 LEARN_DYN_FIXED, LEARN_DYN_ENV = 0, 1  # rmx_learn_config.dynamics
+LEARN_RUN_MAX = 4096  # RMX_LEARN_RUN_MAX
 SYNC_MAX_ENVS = 256  # RMX_SYNC_MAX_ENVS
 QUEUE_INFO_N = 7  # RMX_QUEUE_INFO_N
 QUEUE_STATES = ("unused", "ready", "unavailable", "retired")  # RMX_QUEUE_*
@@ -58,7 +59,7 @@ HASHED_SOURCES = ("rmx_kernels.hip", "rmx_fast.hip", "rmx_fast_step.inc", "rmx_s
                   "rmx_queue.cpp", "rmx_tables.cpp",
                   "rmx_handle.h", "rmx_capi_create.cpp", "rmx_capi_sync.cpp", "rmx_capi_seq.cpp", "rmx_capi_learn.cpp", "rmx_capi_state.cpp",
                   "rmx_comd.cpp", "rmx_build_info.cpp", "rmx_internal.h", "rmx_layout.h", "rmx_host.h", "rmx_device.h",
-                  "rmx_generic.h", "rmx_comd.h", "rmx_hoststep.cpp", "rmx_hoststep.h", "rmx_learn.hip", "rmx_learn.h",
+                  "rmx_generic.h", "rmx_comd.h", "rmx_hoststep.cpp", "rmx_hoststep.h", "rmx_learn.hip", "rmx_learn_run.hip", "rmx_learn.h",
                   "rmx_rules.h", "../../include/rmx.h",
                   "Makefile")
 
@@ -236,6 +237,7 @@ def load_library(path: str = None, check_source: bool = True):
         "rmx_learn_bind": (C.c_int, [vp, C.POINTER(RmxLearnConfig), vp, vp]),
         "rmx_learn_step": (C.c_int, [vp, vp, C.c_int, vp]),
         "rmx_learn_step_policy": (C.c_int, [vp, C.c_double, C.c_int, u64, i64, C.c_int, vp, vp]),
+        "rmx_learn_run": (C.c_int, [vp, C.c_int32, C.c_double, C.c_int, u64, i64, vp, vp]),
         "rmx_learn_rng_bind": (C.c_int, [vp, vp]),
         "rmx_learn_rng_seed": (C.c_int, [vp, vp, vp]),
         "rmx_learn_lambda_slots": (C.c_int, [vp, C.POINTER(C.c_int32)]),

@@ -139,6 +139,48 @@ class VecQLearning:
                     "rmx_learn_step_policy")
         return actions_out
 
+    def run(self, T, epsilon, seed=None, t_global=None, best=False, learn=True, reference_stream=False,
+            actions_out=None):
+        """``T`` consecutive auto-resetting ``act_step``s (global steps ``t_global .. t_global + T - 1``) in one
+        launch on a GPU env (rmx_learn_run; csrc/rmx_learn_run.hip): the tables, every column, the generators and the
+        trace lists end as the T single steps leave them, bit for bit, and the return sum of the episode statistics
+        agrees to rounding (it is summed in another order).  ``actions_out``: a contiguous int32 ``[T, A, N]`` tensor
+        (an array on a host env) that receives every step's actions.  A ``T`` above ``RMX_LEARN_RUN_MAX`` is split
+        into consecutive calls.  A run pays one launch and one Python call for T steps and touches the state and
+        output columns once: at config 2 with QRM a step inside run(1000) takes 0.63 of a step called on its own at
+        64 envs, 0.70 at 4,096 and 0.73 at 65,536 (profiles/learn_run.md; worlds of five or more agents have not been
+        timed)."""
+        env = self.env
+        T = int(T)
+        if T < 1:
+            raise ValueError("T must be >= 1")
+        if reference_stream:
+            if self.rng is None:
+                raise RuntimeError("run(reference_stream=True) needs policy_seeds at construction")
+            seed = t_global = 0
+        elif seed is None or t_global is None:
+            raise ValueError("the engine's policy needs seed and t_global")
+        p, AN = None, env.A * env.N
+        if actions_out is not None:
+            if self.host:
+                p = env._out(actions_out, np.int32, T * AN, "actions_out").ctypes.data
+            else:
+                t = env.torch
+                if actions_out.dtype is not t.int32 or actions_out.get_device() != env.device.index or \
+                        not actions_out.is_contiguous() or actions_out.numel() < T * AN:
+                    raise ValueError("actions_out must be a contiguous int32 [T, A, N] tensor on the engine's device")
+                p = actions_out.data_ptr()
+        flags = (_capi.LEARN_UPDATE if learn else 0) | (_capi.LEARN_BEST if best else 0) | \
+            (_capi.LEARN_NUMPY if reference_stream else 0)
+        done = 0
+        while done < T:  # the cap of one launch is invisible from here
+            n = min(T - done, _capi.LEARN_RUN_MAX)
+            _capi.check(self.lib.rmx_learn_run(env._h, n, float(epsilon), flags, int(seed) & (2**64 - 1),
+                                               int(t_global) + done, None if p is None else p + 4 * done * AN,
+                                               self._stream()), "rmx_learn_run")
+            done += n
+        return actions_out
+
     def rng_state(self, a, e):
         """Learner (a, e)'s generator as numpy's own ``bit_generator.state`` dict (hand it to a real ``Generator``)."""
         if self.rng is None:
