@@ -423,8 +423,10 @@ int rmx_step_info(const rmx_handle* h, int64_t* out, int32_t n);
  *   touches the buffer.
  *   With RMX_LEARN_BEST as well, best wins: nothing is drawn and the column is not touched.  Without
  *   RMX_LEARN_UPDATE the draws still happen (select_action without update_policy).
- * Bit-exactness of a run: with epsilon fixed (the runners never call learn_done_episode, so epsilon stays at
- * epsilon_start) and float32 rewards as above, the actions of every step, q, visits and each generator's state after T
+ * Bit-exactness of a run: with epsilon as the reference's learner has it (both worlds' reset() call learn_done_episode
+ * on every QLearning learner, ma_frozen_lake.py:86-88, ma_office.py:107-108; the runner scripts pin epsilon_start ==
+ * epsilon_end, so there a fixed scalar epsilon serves; every other schedule: rmx_learn_eps_bind, "per-learner epsilon
+ * schedules" below) and float32 rewards as above, the actions of every step, q, visits and each generator's state after T
  * steps equal those of the runner's loop (select_action for every agent, rm_env.step, update_policy for every agent)
  * bit for bit, on the device and on the host, whatever the sharding (a learner's stream depends on its own column
  * words only).  With RMX_LEARN_DYN_ENV this holds on slip and random-start worlds too, whose episodes the loop resets
@@ -534,8 +536,10 @@ int rmx_learn_rng_seed(rmx_handle* h, const uint64_t* seeds_host /* [A][N] */, v
  * rmx_rollout and the synchronous steps leave the lists alone, their auto-resets included: a caller who mixes them in
  * calls rmx_learn_traces_clear.  A step without RMX_LEARN_UPDATE touches no list but for the wipe above; nor does an
  * action without a table column, nor an experience whose s or sn is outside the agent's rows.
- * reset() does not call learn_done_episode on a QLearningLambda, so epsilon stays fixed.  Not reproduced: an explicit
- * next_action, softmax action selection, epsilon decay.  The arrays are not part of rmx_get_state.
+ * reset() does not call learn_done_episode on a QLearningLambda (it is no QLearning), so under the reference's
+ * runners its epsilon stays fixed: leave the schedule unbound.  The class has a learn_done_episode of its own; a user
+ * loop that calls it at every reset is what a bound schedule reproduces ("per-learner epsilon schedules" below).  Not
+ * reproduced: an explicit next_action, softmax action selection.  The arrays are not part of rmx_get_state.
  * rmx_learn_lambda_bind: a NULL idx unbinds (Q-learning again); a later rmx_learn_bind drops the binding.  A device
  * handle takes device pointers, a host handle host pointers; the extents (A*cap*N, A*cap*N, A*N) cannot be checked.
  * RMX_E_INVALID with a message, before any device work: lambd not finite or outside [0, 1], cap < 1 or cap > 4*S_max,
@@ -546,6 +550,40 @@ int rmx_learn_lambda_slots(const rmx_handle* h, int32_t* l_full);
 int rmx_learn_lambda_bind(rmx_handle* h, double lambd, int32_t cap, int32_t* trace_idx, double* trace_val,
                           int32_t* trace_cnt);
 int rmx_learn_traces_clear(rmx_handle* h, const uint8_t* env_mask_dev, void* hip_stream);
+
+/* ---- per-learner epsilon schedules: the reference's per-episode decay ---------------------------------------
+ * QLearning owns its epsilon (qlearning.py:30-33; defaults epsilon_start = 1.0, epsilon_end = 0.2, epsilon_decay =
+ * 0.99) and learn_done_episode (qlearning.py:153-155) sets epsilon = max(epsilon_end, epsilon * epsilon_decay).  Both
+ * worlds' reset() call it on every QLearning learner at every reset (ma_frozen_lake.py:86-88, ma_office.py:107-108).
+ * rmx_learn_eps_bind, after rmx_learn_bind, gives every learner its own epsilon: a caller-owned column like q, visits
+ * and the generator column, float64 eps[A][N], learner (a, e) at eps[a*N + e], 8-byte aligned; a device handle takes a
+ * device pointer, a host handle a host pointer; the caller fills it with epsilon_start, or with anything per learner
+ * (an epsilon sweep across the replicas); NULL unbinds; the extent (A*N) cannot be checked; the column is not part of
+ * rmx_get_state.  A later rmx_learn_bind drops the binding, as it drops the trace lists.
+ * With a column bound, in rmx_learn_step_policy and rmx_learn_run learner (a, e) explores iff its draw is
+ * < eps[a*N + e], under the engine's hashed policy and under RMX_LEARN_NUMPY alike (the draws themselves are as
+ * without a column).  The scalar epsilon argument is validated as ever and otherwise ignored.  There is no flag bit:
+ * the binding is state, as rmx_learn_lambda_bind's is.
+ * Decay: an auto-reset of env e performed by a learn step (rmx_learn_step, rmx_learn_step_policy, every step of
+ * rmx_learn_run) is the reference's env.reset(): each of the env's A learners gets x = eps*eps_decay (one IEEE float64
+ * multiply), then eps = x > eps_end ? x : eps_end (Python's max(epsilon_end, x)), before the policy reads the column,
+ * with or without RMX_LEARN_UPDATE, and under RMX_LEARN_BEST too (the reference's greedy episodes also go through
+ * reset()).  autoreset = 0 resets nothing and decays nothing.  The result equals the reference's epsilon bit for bit.
+ * Everything outside learn steps leaves the column alone, auto-resets included: rmx_reset, rmx_reset_sync,
+ * rmx_set_state, rmx_step*, rmx_step_seq, rmx_rollout and the synchronous steps (unlike the trace lists, which the
+ * resets empty).  How many resets precede the first step is the caller's business (the FrozenLake runner resets twice,
+ * a plain loop once): rmx_learn_eps_decay(h, env_mask, stream) is learn_done_episode for every learner of the masked
+ * envs (uint8 [N], NULL: all; a device handle takes a device mask, a host handle host bytes), in stream order.
+ * Q(lambda) handles are served identically (see that section for what the reference does there).
+ * Column values are not validated; the explore test is the plain float64 comparison draw < eps with draw in [0, 1):
+ * a value > 1 always explores, a value <= 0 (and -0.0) never does, a NaN never does (every comparison with NaN is
+ * false); a decay lifts every entry that is not above eps_end to eps_end, a NaN entry included (NaN > eps_end is
+ * false), so such values last until the learner's env next resets.
+ * RMX_E_STATE: either call before rmx_learn_bind, rmx_learn_eps_decay with no column bound.  RMX_E_INVALID: a NULL
+ * handle, a misaligned column, eps_end outside [0, 1], eps_decay not finite or outside [0, 1].  Each with a message,
+ * before any device work. */
+int rmx_learn_eps_bind(rmx_handle* h, double* eps /* [A][N]; NULL unbinds */, double eps_end, double eps_decay);
+int rmx_learn_eps_decay(rmx_handle* h, const uint8_t* env_mask /* NULL: all */, void* hip_stream);
 
 /* Synchronise and report kernel-side errors (e.g. RMX_E_ACTION), then clear them. */
 int rmx_check_errors(rmx_handle* h);

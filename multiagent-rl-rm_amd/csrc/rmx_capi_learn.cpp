@@ -1,5 +1,6 @@
 // rmx_capi_learn.cpp — the tabular Q-learning / QRM learner fused into the step (rmx_learn.h, rmx_learn.hip): the
-// rmx_learn_* entry points, the Q(lambda) binding and its trace lists included.  Owns rmx_handle::learn.
+// rmx_learn_* entry points, the Q(lambda) binding with its trace lists and the epsilon schedule included.  Owns
+// rmx_handle::learn.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -33,8 +34,9 @@ static int do_learn_step(rmx_handle* h, const int32_t* actions, rmx::LearnCall l
   p.autoreset = autoreset ? 1 : 0;
   // slip / random starts (a learner bound with RMX_LEARN_DYN_ENV): the kernel reads and writes the env generator and
   // episode columns rmx_bind required, and none of the fast path's caches (the reset cache, the next-episode shuffles)
-  HIP_TRY(rmx::launch_learn_step(p, h->learn.params, lc, h->learn.lam_on ? &h->learn.lam : nullptr, h->cfg.kind,
-                                 h->tables_bytes, as_stream(stream)),
+  HIP_TRY(rmx::launch_learn_step(p, h->learn.params, lc, h->learn.lam_on ? &h->learn.lam : nullptr,
+                                 h->learn.eps.col ? &h->learn.eps : nullptr, h->cfg.kind, h->tables_bytes,
+                                 as_stream(stream)),
           "learn step launch");
   return RMX_OK;
 }
@@ -100,6 +102,7 @@ int rmx_learn_bind(rmx_handle* h, const rmx_learn_config* lc, double* q, double*
     h->host->learn = lp;
     h->host->learn_on = true;
     h->host->lam_on = false;  // a new learner: Q-learning until rmx_learn_lambda_bind
+    h->host->eps = {};        // and the scalar epsilon until rmx_learn_eps_bind
     return RMX_OK;
   }
   if ((reinterpret_cast<uintptr_t>(q) & 15u) || (reinterpret_cast<uintptr_t>(visits) & 15u))
@@ -114,6 +117,7 @@ int rmx_learn_bind(rmx_handle* h, const rmx_learn_config* lc, double* q, double*
   h->learn.params = lp;
   h->learn.on = true;
   h->learn.lam_on = false;  // a new learner: Q-learning until rmx_learn_lambda_bind
+  h->learn.eps = {};        // and the scalar epsilon until rmx_learn_eps_bind
   return RMX_OK;
 }
 
@@ -212,6 +216,41 @@ int rmx_learn_traces_clear(rmx_handle* h, const uint8_t* env_mask_dev, void* str
   return lambda_clear(h, env_mask_dev, stream);
 }
 
+int rmx_learn_eps_bind(rmx_handle* h, double* eps, double eps_end, double eps_decay) {
+  if (!h) return fail(RMX_E_INVALID, "handle is NULL");
+  if (!(h->host ? h->host->learn_on : h->learn.on))
+    return fail(RMX_E_STATE, "no learner bound (rmx_learn_bind comes before rmx_learn_eps_bind)");
+  rmx::EpsParams ep{};
+  if (eps) {  // (NULL: back to the call's scalar epsilon; eps_end and eps_decay are not looked at)
+    if (reinterpret_cast<uintptr_t>(eps) & 7u) return fail(RMX_E_INVALID, "the epsilon column must be 8-byte aligned");
+    if (!(eps_end >= 0.0 && eps_end <= 1.0)) return fail(RMX_E_INVALID, "eps_end must be in [0, 1]");
+    if (!(eps_decay >= 0.0 && eps_decay <= 1.0)) return fail(RMX_E_INVALID, "eps_decay must be finite and in [0, 1]");
+    ep = {eps, eps_end, eps_decay};
+  }
+  if (h->host)
+    h->host->eps = ep;
+  else
+    h->learn.eps = ep;
+  return RMX_OK;
+}
+
+int rmx_learn_eps_decay(rmx_handle* h, const uint8_t* env_mask, void* stream) {
+  if (!h) return fail(RMX_E_INVALID, "handle is NULL");
+  if (!(h->host ? h->host->learn_on : h->learn.on))
+    return fail(RMX_E_STATE, "no learner bound (rmx_learn_bind comes before rmx_learn_eps_decay)");
+  if (!(h->host ? h->host->eps.col : h->learn.eps.col))
+    return fail(RMX_E_STATE, "no epsilon column bound (rmx_learn_eps_bind)");
+  if (h->host) {
+    h->host->eps_decay(env_mask);
+    return RMX_OK;
+  }
+  SYNC_END_OR_RETURN(h);
+  HIP_TRY(hipSetDevice(h->device), "hipSetDevice");
+  HIP_TRY(rmx::launch_eps_decay(h->learn.eps, env_mask, h->cfg.n_agents, h->cfg.n_envs, as_stream(stream)),
+          "epsilon decay launch");
+  return RMX_OK;
+}
+
 int rmx_learn_step(rmx_handle* h, const int32_t* actions, int autoreset, void* stream) {
   rmx::LearnCall lc{};
   lc.update = 1;
@@ -265,8 +304,9 @@ int rmx_learn_run(rmx_handle* h, int32_t T, double epsilon, int flags, uint64_t 
   p.seed = seed;
   p.t_global = t_global;
   p.autoreset = 1;
-  HIP_TRY(rmx::launch_learn_run(p, h->learn.params, lc, h->learn.lam_on ? &h->learn.lam : nullptr, T, h->cfg.kind,
-                                h->tables_bytes, as_stream(stream)),
+  HIP_TRY(rmx::launch_learn_run(p, h->learn.params, lc, h->learn.lam_on ? &h->learn.lam : nullptr,
+                                h->learn.eps.col ? &h->learn.eps : nullptr, T, h->cfg.kind, h->tables_bytes,
+                                as_stream(stream)),
           "learn run launch");
   return RMX_OK;
 }

@@ -134,6 +134,8 @@ struct rmx_handle {
     // rmx_learn_lambda_bind: the learners are Q(lambda) ones over the caller's trace lists (lam_on)
     rmx::LambdaParams lam{};
     bool lam_on = false;
+    // rmx_learn_eps_bind: the per-learner epsilon schedule over the caller's column [A][N] (eps.col == NULL: none)
+    rmx::EpsParams eps{};
   } learn;
 };
 

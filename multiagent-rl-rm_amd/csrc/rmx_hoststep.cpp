@@ -200,6 +200,14 @@ void HostEngine::traces_clear(const uint8_t* mask) {
   }
 }
 
+void HostEngine::eps_decay(const uint8_t* mask) {
+  const int64_t N = cfg.n_envs;
+  for (int64_t e = 0; e < N; ++e) {
+    if (mask && !mask[e]) continue;
+    learn_eps_reset(eps, cfg.n_agents, N, e);
+  }
+}
+
 uint32_t HostEngine::step(const int32_t* actions, int autoreset, bool hashed, uint64_t seed, int64_t t_global,
                           float* trace, const LearnCall* lc) {
   if (cfg.kind == RMX_FROZEN_LAKE)
@@ -234,8 +242,12 @@ uint32_t HostEngine::step_kind(const int32_t* actions, int autoreset, bool hashe
     }
     Pcg rng = {0, 0, 0, 0};
     if (rng_on) rng = {buf.rng[e], buf.rng[N + e], buf.rng[2 * N + e], buf.rng[3 * N + e]};
-    if (autoreset && (s[0].f & RMX_F_ENV_DONE)) {  // the loop's reset() before this step
+    const bool was_reset = autoreset && (s[0].f & RMX_F_ENV_DONE);
+    if (was_reset) {  // the loop's reset() before this step
       reset_regs(s, t, p);
+      // a learn step's reset is learn_done_episode for every agent's learner: a policy step decays where it reads the
+      // learner's epsilon below, a step on the caller's actions here (as the kernel)
+      if (lc && !lc->policy && eps.col) learn_eps_reset(eps, A, N, e);
       if (lc && lam_on)  // a learn step's reset clears the traces of every agent's learner
         for (int a = 0; a < A; ++a) lam.cnt[(int64_t)a * N + e] = 0;
       if (rng_on) {  // env.rng = default_rng(seed of the next episode)
@@ -254,17 +266,19 @@ uint32_t HostEngine::step_kind(const int32_t* actions, int autoreset, bool hashe
         const double* row = (uint64_t)st < (uint64_t)mdp_states(a)
                                 ? learn.q + (((int64_t)a * N + e) * learn.s_max + st) * 4
                                 : none;
+        // the learner's own epsilon with a schedule bound (decayed under RMX_LEARN_BEST too), else the call's
+        const double epsilon = eps.col ? learn_eps_step(eps, a, N, e, was_reset) : lc->epsilon;
         if (lc->policy == kLearnNumpy && !lc->best) {  // the learner's own numpy generator (RMX_LEARN_NUMPY)
           const int64_t plane = (int64_t)A * N;
           uint64_t* w = lc->rng + (int64_t)a * N + e;
           const uint64_t w4 = w[4 * plane];
           LearnRng r = {{w[0], w[plane], w[2 * plane], w[3 * plane]}, (uint32_t)(w4 >> 32), (uint32_t)w4};
-          act[a] = learn_policy_numpy(r, lc->epsilon, row[0], row[1], row[2], row[3]);
+          act[a] = learn_policy_numpy(r, epsilon, row[0], row[1], row[2], row[3]);
           w[0] = r.hi;
           w[plane] = r.lo;
           if (learn_rng_word4(r) != w4) w[4 * plane] = learn_rng_word4(r);
         } else {
-          act[a] = learn_policy(seed, t_global, cfg.n_envs_global, cfg.env_offset + e, A, a, lc->epsilon, lc->best,
+          act[a] = learn_policy(seed, t_global, cfg.n_envs_global, cfg.env_offset + e, A, a, epsilon, lc->best,
                                 row[0], row[1], row[2], row[3]);
         }
         if (lc->actions_out) lc->actions_out[(int64_t)a * N + e] = act[a];

@@ -70,6 +70,11 @@ struct HostEngine {
   // rmx_learn_lambda_bind: Q(lambda) learners over the caller's trace lists (host pointers)
   LambdaParams lam{};
   bool lam_on = false;
+  // rmx_learn_eps_bind: the per-learner epsilon schedule over the caller's column [A][N] (col == NULL: none); only
+  // learn steps and eps_decay touch it
+  EpsParams eps{};
+  // learn_done_episode of every agent's learner of the masked envs (NULL: every env); a column must be bound
+  void eps_decay(const uint8_t* mask);
   // cnt[a][e] = 0 for the masked envs (NULL: every env); nothing without Q(lambda) bound
   void traces_clear(const uint8_t* mask);
 
@@ -82,7 +87,8 @@ struct HostEngine {
   // action outside [0, 4] (or "wait" under FrozenLake slip) was stepped (as wait)
   // lc != NULL: a learn step (rmx_learn_step / rmx_learn_step_policy): the policy's actions when lc->policy (seed,
   // t_global are then the policy hash's; lc->policy == kLearnNumpy: the learners' own generators in lc->rng), the
-  // bound learner's update when lc->update (lam_on: the Q(lambda) sweep, and the lists emptied on auto-reset)
+  // bound learner's update when lc->update (lam_on: the Q(lambda) sweep, and the lists emptied on auto-reset);
+  // eps.col: the epsilon schedule, decayed at the env's auto-reset and read per learner by the policy
   uint32_t step(const int32_t* actions, int autoreset, bool hashed = false, uint64_t seed = 0, int64_t t_global = 0,
                 float* trace = nullptr, const LearnCall* lc = nullptr);
   void fill_actions(uint64_t seed, int64_t t0, int32_t T, int32_t* out) const;

@@ -370,12 +370,20 @@ hipError_t launch_mdp(const KParams& p, int kind, int ag, int fix_fl, int64_t S,
 // the learn step (rmx_learn.hip): the thread-per-env step over the generic tables plus every learner's update
 // lam != NULL: the Q(lambda) learn step over the bound trace lists (one launch, like the other)
 hipError_t launch_learn_step(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
-                             int kind, size_t lds, hipStream_t st);
+                             const EpsParams* eps, int kind, size_t lds, hipStream_t st);
 // T consecutive auto-reset learn steps with the engine's or the learners' own policy in one launch (rmx_learn_run.hip)
 hipError_t launch_learn_run(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
-                            int32_t T, int kind, size_t lds, hipStream_t st);
+                            const EpsParams* eps, int32_t T, int kind, size_t lds, hipStream_t st);
+// The two above with a per-learner epsilon schedule (eps != NULL), which they hand over to: the kernels' EPS
+// instantiations, compiled in rmx_learn_eps.hip / rmx_learn_run_eps.hip
+hipError_t launch_learn_step_eps(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
+                                 const EpsParams* eps, int kind, size_t lds, hipStream_t st);
+hipError_t launch_learn_run_eps(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
+                                const EpsParams* eps, int32_t T, int kind, size_t lds, hipStream_t st);
 // cnt[a][e] = 0 for every env of the device mask (NULL: every env)
 hipError_t launch_traces_clear(int32_t* cnt, const uint8_t* mask, int A, int64_t N, hipStream_t st);
+// rmx_learn_eps_decay: learn_done_episode of every agent's learner of every env of the device mask (NULL: every env)
+hipError_t launch_eps_decay(const EpsParams& ep, const uint8_t* mask, int A, int64_t N, hipStream_t st);
 constexpr int kStatsPartials = 512;  // max blocks of each partial pass of the stats reduction
 constexpr int kStatsEnvsPerThread = 4;  // per-env slots summed by each thread of the stats launch
 // sums the per-wave slab and, if es_ret != NULL, the per-env slots of the fast path (FastParams: one row [N]

@@ -17,6 +17,8 @@
 #pragma once
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "rmx_rules.h"
 
 #if defined(__clang__)
@@ -39,6 +41,24 @@ struct LearnParams {
   int64_t s_max;  // W * H * max_a enc_nq[a]
   int32_t use_qrm, use_rsh, trunc_is_terminal;
 };
+
+// The per-learner epsilon schedule bound by rmx_learn_eps_bind (include/rmx.h, "per-learner epsilon schedules"): the
+// caller's column float64 [A][N], learner (a, e) at a * N + e, and QLearning's epsilon_end / epsilon_decay.  col == NULL:
+// no schedule, the call's scalar epsilon (LearnCall::epsilon) serves every learner.
+struct EpsParams {
+  double* col;
+  double end, decay;
+};
+
+// The learn kernels take the LambdaParams and the EpsParams as trailing arguments of their own, each only in the
+// instantiations that use it (a pack, empty for the others): the argument of type T among them.
+template <typename T, typename First, typename... Rest>
+RMX_HD const T& learn_extra(const First& first, const Rest&... rest) {
+  if constexpr (std::is_same_v<T, First>)
+    return first;
+  else
+    return learn_extra<T>(rest...);
+}
 
 // Per-call arguments of a learn step.
 struct LearnCall {
@@ -80,6 +100,35 @@ RMX_LEARN_NOFMA_ATTR RMX_HD double learn_reward(float renv, float modifier, floa
   RMX_LEARN_NOFMA
   const double m = (double)modifier * (double)rq;
   return (double)renv + m;
+}
+
+// learn_done_episode (qlearning.py:153-155): epsilon = max(epsilon_end, epsilon * epsilon_decay).  One multiply, then
+// Python's max(end, x): x only where x > end (a NaN product gives end).
+RMX_LEARN_NOFMA_ATTR RMX_HD double learn_eps_decay(double eps, double end, double decay) {
+  RMX_LEARN_NOFMA
+  const double x = eps * decay;
+  return x > end ? x : end;
+}
+
+// env.reset()'s learn_done_episode of every agent's learner of env e (ma_frozen_lake.py:86-88, ma_office.py:107-108): a
+// learn step's auto-reset, before the policy reads the column
+RMX_HD void learn_eps_reset(const EpsParams& ep, int A, int64_t N, int64_t e) {
+  for (int a = 0; a < A; ++a) {
+    double* c = ep.col + (int64_t)a * N + e;
+    *c = learn_eps_decay(*c, ep.end, ep.decay);
+  }
+}
+
+// The epsilon learner (a, e) explores under in a policy step with a schedule bound: its column entry (one 8-B load,
+// contiguous over a wave's envs), decayed and stored first when the step has just auto-reset the env.
+RMX_HD double learn_eps_step(const EpsParams& ep, int a, int64_t N, int64_t e, bool was_reset) {
+  double* c = ep.col + (int64_t)a * N + e;
+  double eps = *c;
+  if (was_reset) {
+    eps = learn_eps_decay(eps, ep.end, ep.decay);
+    *c = eps;
+  }
+  return eps;
 }
 
 RMX_HD double learn_max4(double a, double b, double c, double d) {  // np.max of a row

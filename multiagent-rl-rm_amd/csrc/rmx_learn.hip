@@ -22,6 +22,11 @@
 // learner's own list of live traces (rmx_learn.h; slot-major [A][cap][N], so a wave's read of slot j is contiguous), in
 // batches of independent read-modify-writes, and the auto-reset empties the env's lists before the policy reads its
 // rows.  Tail lanes and the agents past A touch no list.
+// With EPS (rmx_learn_eps_bind: a per-learner epsilon schedule) a policy step loads each learner's epsilon from the
+// column float64 [A][N] (one coalesced 8-B load per lane, beside the row load it does not depend on); a lane that has
+// just auto-reset its env decays the value first and stores it.  A step on the caller's actions decays in the reset
+// itself.  The EPS kernels are instantiated in a translation unit of their own (rmx_learn_eps.hip, which includes this
+// file): the kernels of a handle without a schedule are the ones it always ran, instruction for instruction.
 //
 // Reference semantics: rmx_learn.h (update, experiences, policy, the Q(lambda) sweep), rmx_kernels.hip (the step).
 #include <hip/hip_runtime.h>
@@ -35,18 +40,23 @@
 
 namespace rmx {
 
+#ifdef RMX_LEARN_EPS_TU
+#define RMX_LAUNCH_LEARN_STEP launch_learn_step_eps
+#else
+#define RMX_LAUNCH_LEARN_STEP launch_learn_step
+#endif
+
 // POLICY: kLearnActions (the caller's actions), kLearnHash (the engine's hash policy) or kLearnNumpy (each learner's
 // numpy generator, read from and written back to lc.rng); everything the third adds sits behind if constexpr.
 // STOCH: the env's own generator (slip, the per-episode reseed, random starts), likewise behind if constexpr.
 // LAMBDA: the Q(lambda) learners (rmx_learn_lambda_bind): the auto-reset empties the env's trace lists and the update
 // is learn_lambda_agent's sweep over the learner's list; behind if constexpr, as the other two.
-// LAM is the one LambdaParams argument of the LAMBDA kernels and empty for the others, whose signature (and code) is
-// that of the kernel without Q(lambda).
-__device__ __forceinline__ const LambdaParams& lambda_of(const LambdaParams& lam) { return lam; }
-
-template <int KIND, int AMAX, int POLICY, bool STOCH, bool LAMBDA, typename... LAM>
-__global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams lp, LearnCall lc, LAM... lam_arg) {
-  static_assert(sizeof...(LAM) == (LAMBDA ? 1 : 0), "LAMBDA kernels take the LambdaParams, the others nothing");
+// EPS: the per-learner epsilon schedule (rmx_learn_eps_bind), behind if constexpr as well.
+// XP: the LambdaParams argument of the LAMBDA kernels, then the EpsParams argument of the EPS kernels; empty for the
+// others, whose signature (and code) is that of the kernel without either (learn_extra<T>, rmx_learn.h, picks one).
+template <int KIND, int AMAX, int POLICY, bool STOCH, bool LAMBDA, bool EPS, typename... XP>
+__global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams lp, LearnCall lc, XP... xp) {
+  static_assert(sizeof...(XP) == (LAMBDA ? 1 : 0) + (EPS ? 1 : 0), "one argument each for LAMBDA and EPS, else none");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int64_t N = p.N;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -83,10 +93,15 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
   if (live) {
     Pcg rng = {0, 0, 0, 0};
     if constexpr (STOCH) rng = {p.rng[e], p.rng[N + e], p.rng[2 * N + e], p.rng[3 * N + e]};
+    bool was_reset = false;  // (read by the EPS kernels only)
     if (p.autoreset && (s[0].f & RMX_F_ENV_DONE)) {
+      was_reset = true;
       reset_regs<AMAX>(s, t, p);
+      // env.reset() is learn_done_episode for every agent's learner (rmx_learn_eps_bind).  A policy step decays where
+      // it reads the learner's epsilon below; a step on the caller's actions reads none and decays here.
+      if constexpr (EPS && POLICY == kLearnActions) learn_eps_reset(learn_extra<EpsParams>(xp...), p.A, N, e);
       if constexpr (LAMBDA) {  // env.reset() clears the traces of every agent's learner (ma_frozen_lake.py:77-81)
-        const LambdaParams& lam = lambda_of(lam_arg...);
+        const LambdaParams& lam = learn_extra<LambdaParams>(xp...);
 #pragma unroll
         for (int a = 0; a < AMAX; ++a)
           if (AMAX <= 4 || a < p.A) lam.cnt[(int64_t)a * N + e] = 0;
@@ -113,24 +128,27 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
             lo = row[0];
             hi = row[1];
           }
+          double eps = lc.epsilon;
+          if constexpr (EPS)  // (decays under RMX_LEARN_BEST too)
+            eps = learn_eps_step(learn_extra<EpsParams>(xp...), a, N, e, was_reset);
           if constexpr (POLICY == kLearnNumpy) {
             if (lc.best) {  // no draw: the column is not touched
-              act[a] = learn_policy(0, 0, 0, 0, p.A, a, lc.epsilon, 1, lo.x, lo.y, hi.x, hi.y);
+              act[a] = learn_policy(0, 0, 0, 0, p.A, a, eps, 1, lo.x, lo.y, hi.x, hi.y);
             } else {
               // the learner's five words, plane-major: each a coalesced 8-B load per lane
               const int64_t plane = (int64_t)p.A * N;
               uint64_t* w = lc.rng + (int64_t)a * N + e;
               const uint64_t w4 = w[4 * plane];
               LearnRng r = {{w[0], w[plane], w[2 * plane], w[3 * plane]}, (uint32_t)(w4 >> 32), (uint32_t)w4};
-              act[a] = learn_policy_numpy(r, lc.epsilon, lo.x, lo.y, hi.x, hi.y);
+              act[a] = learn_policy_numpy(r, eps, lo.x, lo.y, hi.x, hi.y);
               w[0] = r.hi;
               w[plane] = r.lo;
               const uint64_t n4 = learn_rng_word4(r);
               if (n4 != w4) w[4 * plane] = n4;  // (the increment never changes)
             }
           } else {
-            act[a] = learn_policy(p.seed, p.t_global, p.n_global, p.env_offset + e, p.A, a, lc.epsilon, lc.best, lo.x,
-                                  lo.y, hi.x, hi.y);
+            act[a] = learn_policy(p.seed, p.t_global, p.n_global, p.env_offset + e, p.A, a, eps, lc.best, lo.x, lo.y,
+                                  hi.x, hi.y);
           }
           if (lc.actions_out) lc.actions_out[(int64_t)a * N + e] = act[a];
         }
@@ -183,7 +201,7 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
                                 s[a].q,         o[a].env_term, o[a].term, o[a].trunc, o[a].renv};
           const int64_t base = ((int64_t)a * N + e) * lp.s_max * 4;
           if constexpr (LAMBDA)
-            full |= learn_lambda_agent(lp, lambda_of(lam_arg...), T, st, lp.q + base,
+            full |= learn_lambda_agent(lp, learn_extra<LambdaParams>(xp...), T, st, lp.q + base,
                                        lp.visits ? lp.visits + base : nullptr, act[a], (int64_t)p.HW * p.enc_nq[a], a,
                                        N, e);
           else
@@ -204,56 +222,68 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
   wave_flush_slot(p.slab, slot, ls, __any(done));
 }
 
+template <int KIND, int AMAX, int POLICY, bool STOCH>
+static void launch_learn_p(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
+                           const EpsParams* eps, dim3 g, dim3 b, size_t lds, hipStream_t st) {
+#ifdef RMX_LEARN_EPS_TU  // the EpsParams behind the other arguments
+  if (lam)
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, POLICY, STOCH, true, true, LambdaParams, EpsParams>), g, b, lds, st,
+                       p, lp, lc, *lam, *eps);
+  else
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, POLICY, STOCH, false, true, EpsParams>), g, b, lds, st, p, lp, lc,
+                       *eps);
+#else
+  if (lam)
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, POLICY, STOCH, true, false, LambdaParams>), g, b, lds, st, p, lp, lc,
+                       *lam);
+  else
+    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, POLICY, STOCH, false, false>), g, b, lds, st, p, lp, lc);
+#endif
+}
+
 template <int KIND, int AMAX, bool STOCH>
 static hipError_t launch_learn_t(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
-                                 dim3 g, dim3 b, size_t lds, hipStream_t st) {
-  if (lam) {
-    if (lc.policy == kLearnNumpy)
-      hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnNumpy, STOCH, true, LambdaParams>), g, b, lds, st, p, lp, lc,
-                         *lam);
-    else if (lc.policy)
-      hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnHash, STOCH, true, LambdaParams>), g, b, lds, st, p, lp, lc,
-                         *lam);
-    else
-      hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnActions, STOCH, true, LambdaParams>), g, b, lds, st, p, lp, lc,
-                         *lam);
-    return hipGetLastError();
-  }
+                                 const EpsParams* eps, dim3 g, dim3 b, size_t lds, hipStream_t st) {
   if (lc.policy == kLearnNumpy)
-    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnNumpy, STOCH, false>), g, b, lds, st, p, lp, lc);
+    launch_learn_p<KIND, AMAX, kLearnNumpy, STOCH>(p, lp, lc, lam, eps, g, b, lds, st);
   else if (lc.policy)
-    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnHash, STOCH, false>), g, b, lds, st, p, lp, lc);
+    launch_learn_p<KIND, AMAX, kLearnHash, STOCH>(p, lp, lc, lam, eps, g, b, lds, st);
   else
-    hipLaunchKernelGGL((learn_step_kernel<KIND, AMAX, kLearnActions, STOCH, false>), g, b, lds, st, p, lp, lc);
+    launch_learn_p<KIND, AMAX, kLearnActions, STOCH>(p, lp, lc, lam, eps, g, b, lds, st);
   return hipGetLastError();
 }
 
 template <int KIND, bool STOCH>
 static hipError_t launch_learn_k(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
-                                 dim3 g, dim3 b, size_t lds, hipStream_t st) {
+                                 const EpsParams* eps, dim3 g, dim3 b, size_t lds, hipStream_t st) {
   switch (amax_bucket(p.A)) {
-    case 1: return launch_learn_t<KIND, 1, STOCH>(p, lp, lc, lam, g, b, lds, st);
-    case 2: return launch_learn_t<KIND, 2, STOCH>(p, lp, lc, lam, g, b, lds, st);
-    case 3: return launch_learn_t<KIND, 3, STOCH>(p, lp, lc, lam, g, b, lds, st);
-    case 4: return launch_learn_t<KIND, 4, STOCH>(p, lp, lc, lam, g, b, lds, st);
-    default: return launch_learn_t<KIND, 8, STOCH>(p, lp, lc, lam, g, b, lds, st);
+    case 1: return launch_learn_t<KIND, 1, STOCH>(p, lp, lc, lam, eps, g, b, lds, st);
+    case 2: return launch_learn_t<KIND, 2, STOCH>(p, lp, lc, lam, eps, g, b, lds, st);
+    case 3: return launch_learn_t<KIND, 3, STOCH>(p, lp, lc, lam, eps, g, b, lds, st);
+    case 4: return launch_learn_t<KIND, 4, STOCH>(p, lp, lc, lam, eps, g, b, lds, st);
+    default: return launch_learn_t<KIND, 8, STOCH>(p, lp, lc, lam, eps, g, b, lds, st);
   }
 }
 
 // 256-thread blocks, one thread per env (the per-wave statistics slab is sized for that geometry at rmx_create).
 // p.rng_on (the handle has slip or random starts; the caller has checked the learner's dynamics and the rng / episode
 // columns) selects the STOCH instantiations; every other handle runs the kernels it always ran.
-// lam != NULL: the Q(lambda) kernels.
-hipError_t launch_learn_step(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
-                             int kind, size_t lds, hipStream_t st) {
+// lam != NULL: the Q(lambda) kernels.  eps != NULL: the EPS kernels (launch_learn_step_eps, this function as
+// rmx_learn_eps.hip compiles it).
+hipError_t RMX_LAUNCH_LEARN_STEP(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
+                                 const EpsParams* eps, int kind, size_t lds, hipStream_t st) {
+#ifndef RMX_LEARN_EPS_TU
+  if (eps) return launch_learn_step_eps(p, lp, lc, lam, eps, kind, lds, st);
+#endif
   const dim3 g((unsigned)((p.N + 255) / 256)), b(256);
   if (p.rng_on)
-    return kind == RMX_FROZEN_LAKE ? launch_learn_k<RMX_FROZEN_LAKE, true>(p, lp, lc, lam, g, b, lds, st)
-                                   : launch_learn_k<RMX_OFFICE_WORLD, true>(p, lp, lc, lam, g, b, lds, st);
-  return kind == RMX_FROZEN_LAKE ? launch_learn_k<RMX_FROZEN_LAKE, false>(p, lp, lc, lam, g, b, lds, st)
-                                 : launch_learn_k<RMX_OFFICE_WORLD, false>(p, lp, lc, lam, g, b, lds, st);
+    return kind == RMX_FROZEN_LAKE ? launch_learn_k<RMX_FROZEN_LAKE, true>(p, lp, lc, lam, eps, g, b, lds, st)
+                                   : launch_learn_k<RMX_OFFICE_WORLD, true>(p, lp, lc, lam, eps, g, b, lds, st);
+  return kind == RMX_FROZEN_LAKE ? launch_learn_k<RMX_FROZEN_LAKE, false>(p, lp, lc, lam, eps, g, b, lds, st)
+                                 : launch_learn_k<RMX_OFFICE_WORLD, false>(p, lp, lc, lam, eps, g, b, lds, st);
 }
 
+#ifndef RMX_LEARN_EPS_TU
 // rmx_learn_traces_clear and the resets of a handle with Q(lambda) bound: cnt[a][e] = 0 for the masked envs
 __global__ void __launch_bounds__(256) traces_clear_kernel(int32_t* cnt, const uint8_t* mask, int A, int64_t N) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -265,5 +295,18 @@ hipError_t launch_traces_clear(int32_t* cnt, const uint8_t* mask, int A, int64_t
   hipLaunchKernelGGL(traces_clear_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, cnt, mask, A, N);
   return hipGetLastError();
 }
+
+// rmx_learn_eps_decay: one thread per env decays its agents' column entries (each a coalesced 8-B load and store)
+__global__ void __launch_bounds__(256) eps_decay_kernel(EpsParams ep, const uint8_t* mask, int A, int64_t N) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= N || (mask && !mask[e])) return;
+  learn_eps_reset(ep, A, N, e);
+}
+
+hipError_t launch_eps_decay(const EpsParams& ep, const uint8_t* mask, int A, int64_t N, hipStream_t st) {
+  hipLaunchKernelGGL(eps_decay_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, ep, mask, A, N);
+  return hipGetLastError();
+}
+#endif  // RMX_LEARN_EPS_TU
 
 }  // namespace rmx

@@ -11,6 +11,11 @@
 // the trace lists).  The learners' five generator words are loaded per step from the coalesced column in every
 // bucket: those loads do not depend on the table row the policy waits for and fly beside it, so keeping up to 80
 // VGPRs of generator state live across env_step and the sweep would buy no round trip.
+// With EPS (rmx_learn_eps_bind: a per-learner epsilon schedule) the env's A epsilons do stay in registers over the
+// T-loop, one double per agent: the auto-reset decays them there, the policy reads them there, and a lane whose env
+// reset stores them once at the end.  A reload per step cost 6-7 % of the run at 65,536 envs.  The
+// EPS kernels are instantiated in a translation unit of their own (rmx_learn_run_eps.hip, which includes this file):
+// the kernels of a handle without a schedule are the ones it always ran.
 // actions_out is stored per step ([T][A][N], a coalesced 4-B store per lane); the episode statistics are summed per
 // lane over the whole run and flushed once per wave, as rollout_kernel's (so the return sum is associated differently
 // from T single steps; the integer statistics are equal).
@@ -27,15 +32,18 @@
 
 namespace rmx {
 
-__device__ __forceinline__ const LambdaParams& run_lambda_of(const LambdaParams& lam) { return lam; }
+#ifdef RMX_LEARN_EPS_TU
+#define RMX_LAUNCH_LEARN_RUN launch_learn_run_eps
+#else
+#define RMX_LAUNCH_LEARN_RUN launch_learn_run
+#endif
 
-// POLICY: kLearnHash or kLearnNumpy (a run on the caller's actions is not served); STOCH, LAMBDA, LAM: as
+// POLICY: kLearnHash or kLearnNumpy (a run on the caller's actions is not served); STOCH, LAMBDA, EPS, XP: as
 // learn_step_kernel's.  Auto-reset is always on.
-template <int KIND, int AMAX, int POLICY, bool STOCH, bool LAMBDA, typename... LAM>
-__global__ void __launch_bounds__(256) learn_run_kernel(KParams p, LearnParams lp, LearnCall lc, int32_t T,
-                                                        LAM... lam_arg) {
+template <int KIND, int AMAX, int POLICY, bool STOCH, bool LAMBDA, bool EPS, typename... XP>
+__global__ void __launch_bounds__(256) learn_run_kernel(KParams p, LearnParams lp, LearnCall lc, int32_t T, XP... xp) {
   static_assert(POLICY == kLearnHash || POLICY == kLearnNumpy, "a run chooses its own actions");
-  static_assert(sizeof...(LAM) == (LAMBDA ? 1 : 0), "LAMBDA kernels take the LambdaParams, the others nothing");
+  static_assert(sizeof...(XP) == (LAMBDA ? 1 : 0) + (EPS ? 1 : 0), "one argument each for LAMBDA and EPS, else none");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int64_t N = p.N;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -75,12 +83,30 @@ __global__ void __launch_bounds__(256) learn_run_kernel(KParams p, LearnParams l
       episode = p.episode[e];
     }
   }
+  // EPS: the env's learners' epsilons stay in registers over the T-loop as the state does, loaded once and, when the
+  // env has reset, stored once at the end (a reload per step beside the row was measured: DESIGN.md 4.10.5)
+  double eps[AMAX];
+  bool eps_moved = false;
+  if constexpr (EPS) {
+    if (live) {
+#pragma unroll
+      for (int a = 0; a < AMAX; ++a)
+        if (AMAX <= 4 || a < p.A) eps[a] = learn_extra<EpsParams>(xp...).col[(int64_t)a * N + e];
+    }
+  }
   for (int32_t it = 0; it < T; ++it) {
     if (live) {
       if (s[0].f & RMX_F_ENV_DONE) {
         reset_regs<AMAX>(s, t, p);
+        if constexpr (EPS) {  // env.reset() is learn_done_episode for every agent's learner, before the policy
+          const EpsParams& ep = learn_extra<EpsParams>(xp...);
+          eps_moved = true;
+#pragma unroll
+          for (int a = 0; a < AMAX; ++a)
+            if (AMAX <= 4 || a < p.A) eps[a] = learn_eps_decay(eps[a], ep.end, ep.decay);
+        }
         if constexpr (LAMBDA) {  // env.reset() clears the traces of every agent's learner
-          const LambdaParams& lam = run_lambda_of(lam_arg...);
+          const LambdaParams& lam = learn_extra<LambdaParams>(xp...);
 #pragma unroll
           for (int a = 0; a < AMAX; ++a)
             if (AMAX <= 4 || a < p.A) lam.cnt[(int64_t)a * N + e] = 0;
@@ -105,23 +131,24 @@ __global__ void __launch_bounds__(256) learn_run_kernel(KParams p, LearnParams l
             lo = row[0];
             hi = row[1];
           }
+          const double epsilon = EPS ? eps[a] : lc.epsilon;
           if constexpr (POLICY == kLearnNumpy) {
             if (lc.best) {  // no draw: the column is not touched
-              act[a] = learn_policy(0, 0, 0, 0, p.A, a, lc.epsilon, 1, lo.x, lo.y, hi.x, hi.y);
+              act[a] = learn_policy(0, 0, 0, 0, p.A, a, epsilon, 1, lo.x, lo.y, hi.x, hi.y);
             } else {
               // the learner's five words, plane-major: each a coalesced 8-B load per lane
               const int64_t plane = (int64_t)p.A * N;
               uint64_t* w = lc.rng + (int64_t)a * N + e;
               const uint64_t w4 = w[4 * plane];
               LearnRng r = {{w[0], w[plane], w[2 * plane], w[3 * plane]}, (uint32_t)(w4 >> 32), (uint32_t)w4};
-              act[a] = learn_policy_numpy(r, lc.epsilon, lo.x, lo.y, hi.x, hi.y);
+              act[a] = learn_policy_numpy(r, epsilon, lo.x, lo.y, hi.x, hi.y);
               w[0] = r.hi;
               w[plane] = r.lo;
               const uint64_t n4 = learn_rng_word4(r);
               if (n4 != w4) w[4 * plane] = n4;  // (the increment never changes)
             }
           } else {
-            act[a] = learn_policy(p.seed, p.t_global + it, p.n_global, eg, p.A, a, lc.epsilon, lc.best, lo.x, lo.y,
+            act[a] = learn_policy(p.seed, p.t_global + it, p.n_global, eg, p.A, a, epsilon, lc.best, lo.x, lo.y,
                                   hi.x, hi.y);
           }
           if (lc.actions_out) lc.actions_out[((int64_t)it * p.A + a) * N + e] = act[a];
@@ -149,7 +176,7 @@ __global__ void __launch_bounds__(256) learn_run_kernel(KParams p, LearnParams l
                                   s[a].q,         o[a].env_term, o[a].term, o[a].trunc, o[a].renv};
             const int64_t base = ((int64_t)a * N + e) * lp.s_max * 4;
             if constexpr (LAMBDA)
-              full |= learn_lambda_agent(lp, run_lambda_of(lam_arg...), Tb, st, lp.q + base,
+              full |= learn_lambda_agent(lp, learn_extra<LambdaParams>(xp...), Tb, st, lp.q + base,
                                          lp.visits ? lp.visits + base : nullptr, act[a], (int64_t)p.HW * p.enc_nq[a],
                                          a, N, e);
             else
@@ -169,6 +196,13 @@ __global__ void __launch_bounds__(256) learn_run_kernel(KParams p, LearnParams l
       p.rng[2 * N + e] = rng.ihi;
       p.rng[3 * N + e] = rng.ilo;
       p.episode[e] = episode;
+    }
+    if constexpr (EPS) {
+      if (eps_moved) {
+#pragma unroll
+        for (int a = 0; a < AMAX; ++a)
+          if (AMAX <= 4 || a < p.A) learn_extra<EpsParams>(xp...).col[(int64_t)a * N + e] = eps[a];
+      }
     }
 #pragma unroll
     for (int a = 0; a < AMAX; ++a) {
@@ -198,47 +232,60 @@ __global__ void __launch_bounds__(256) learn_run_kernel(KParams p, LearnParams l
   wave_flush(p.slab, ls, __any(ls.episodes != 0));
 }
 
+template <int KIND, int AMAX, int POLICY, bool STOCH>
+static void launch_run_p(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
+                         const EpsParams* eps, int32_t T, dim3 g, dim3 b, size_t lds, hipStream_t st) {
+#ifdef RMX_LEARN_EPS_TU  // the EpsParams behind the other arguments
+  if (lam)
+    hipLaunchKernelGGL((learn_run_kernel<KIND, AMAX, POLICY, STOCH, true, true, LambdaParams, EpsParams>), g, b, lds, st, p,
+                       lp, lc, T, *lam, *eps);
+  else
+    hipLaunchKernelGGL((learn_run_kernel<KIND, AMAX, POLICY, STOCH, false, true, EpsParams>), g, b, lds, st, p, lp, lc, T,
+                       *eps);
+#else
+  if (lam)
+    hipLaunchKernelGGL((learn_run_kernel<KIND, AMAX, POLICY, STOCH, true, false, LambdaParams>), g, b, lds, st, p, lp, lc,
+                       T, *lam);
+  else
+    hipLaunchKernelGGL((learn_run_kernel<KIND, AMAX, POLICY, STOCH, false, false>), g, b, lds, st, p, lp, lc, T);
+#endif
+}
+
 template <int KIND, int AMAX, bool STOCH>
 static hipError_t launch_run_t(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
-                               int32_t T, dim3 g, dim3 b, size_t lds, hipStream_t st) {
-  if (lam) {
-    if (lc.policy == kLearnNumpy)
-      hipLaunchKernelGGL((learn_run_kernel<KIND, AMAX, kLearnNumpy, STOCH, true, LambdaParams>), g, b, lds, st, p, lp, lc,
-                         T, *lam);
-    else
-      hipLaunchKernelGGL((learn_run_kernel<KIND, AMAX, kLearnHash, STOCH, true, LambdaParams>), g, b, lds, st, p, lp, lc,
-                         T, *lam);
-    return hipGetLastError();
-  }
+                               const EpsParams* eps, int32_t T, dim3 g, dim3 b, size_t lds, hipStream_t st) {
   if (lc.policy == kLearnNumpy)
-    hipLaunchKernelGGL((learn_run_kernel<KIND, AMAX, kLearnNumpy, STOCH, false>), g, b, lds, st, p, lp, lc, T);
+    launch_run_p<KIND, AMAX, kLearnNumpy, STOCH>(p, lp, lc, lam, eps, T, g, b, lds, st);
   else
-    hipLaunchKernelGGL((learn_run_kernel<KIND, AMAX, kLearnHash, STOCH, false>), g, b, lds, st, p, lp, lc, T);
+    launch_run_p<KIND, AMAX, kLearnHash, STOCH>(p, lp, lc, lam, eps, T, g, b, lds, st);
   return hipGetLastError();
 }
 
 template <int KIND, bool STOCH>
 static hipError_t launch_run_k(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
-                               int32_t T, dim3 g, dim3 b, size_t lds, hipStream_t st) {
+                               const EpsParams* eps, int32_t T, dim3 g, dim3 b, size_t lds, hipStream_t st) {
   switch (amax_bucket(p.A)) {
-    case 1: return launch_run_t<KIND, 1, STOCH>(p, lp, lc, lam, T, g, b, lds, st);
-    case 2: return launch_run_t<KIND, 2, STOCH>(p, lp, lc, lam, T, g, b, lds, st);
-    case 3: return launch_run_t<KIND, 3, STOCH>(p, lp, lc, lam, T, g, b, lds, st);
-    case 4: return launch_run_t<KIND, 4, STOCH>(p, lp, lc, lam, T, g, b, lds, st);
-    default: return launch_run_t<KIND, 8, STOCH>(p, lp, lc, lam, T, g, b, lds, st);
+    case 1: return launch_run_t<KIND, 1, STOCH>(p, lp, lc, lam, eps, T, g, b, lds, st);
+    case 2: return launch_run_t<KIND, 2, STOCH>(p, lp, lc, lam, eps, T, g, b, lds, st);
+    case 3: return launch_run_t<KIND, 3, STOCH>(p, lp, lc, lam, eps, T, g, b, lds, st);
+    case 4: return launch_run_t<KIND, 4, STOCH>(p, lp, lc, lam, eps, T, g, b, lds, st);
+    default: return launch_run_t<KIND, 8, STOCH>(p, lp, lc, lam, eps, T, g, b, lds, st);
   }
 }
 
 // The geometry of launch_learn_step (256-thread blocks, one thread per env: the per-wave statistics slab is sized
 // for it at rmx_create).  lc.policy is kLearnHash or kLearnNumpy and 1 <= T (the caller has checked both).
-hipError_t launch_learn_run(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
-                            int32_t T, int kind, size_t lds, hipStream_t st) {
+hipError_t RMX_LAUNCH_LEARN_RUN(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
+                                const EpsParams* eps, int32_t T, int kind, size_t lds, hipStream_t st) {
+#ifndef RMX_LEARN_EPS_TU
+  if (eps) return launch_learn_run_eps(p, lp, lc, lam, eps, T, kind, lds, st);
+#endif
   const dim3 g((unsigned)((p.N + 255) / 256)), b(256);
   if (p.rng_on)
-    return kind == RMX_FROZEN_LAKE ? launch_run_k<RMX_FROZEN_LAKE, true>(p, lp, lc, lam, T, g, b, lds, st)
-                                   : launch_run_k<RMX_OFFICE_WORLD, true>(p, lp, lc, lam, T, g, b, lds, st);
-  return kind == RMX_FROZEN_LAKE ? launch_run_k<RMX_FROZEN_LAKE, false>(p, lp, lc, lam, T, g, b, lds, st)
-                                 : launch_run_k<RMX_OFFICE_WORLD, false>(p, lp, lc, lam, T, g, b, lds, st);
+    return kind == RMX_FROZEN_LAKE ? launch_run_k<RMX_FROZEN_LAKE, true>(p, lp, lc, lam, eps, T, g, b, lds, st)
+                                   : launch_run_k<RMX_OFFICE_WORLD, true>(p, lp, lc, lam, eps, T, g, b, lds, st);
+  return kind == RMX_FROZEN_LAKE ? launch_run_k<RMX_FROZEN_LAKE, false>(p, lp, lc, lam, eps, T, g, b, lds, st)
+                                 : launch_run_k<RMX_OFFICE_WORLD, false>(p, lp, lc, lam, eps, T, g, b, lds, st);
 }
 
 }  // namespace rmx

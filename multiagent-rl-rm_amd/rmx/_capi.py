@@ -30,7 +30,7 @@ EXPORTS = (
     "rmx_code_object_check", "rmx_device_count", "rmx_queue_timing", "rmx_queue_times", "rmx_step_info",
     "rmx_seq_packed", "rmx_learn_states", "rmx_learn_bind", "rmx_learn_step", "rmx_learn_step_policy",
     "rmx_learn_rng_bind", "rmx_learn_rng_seed", "rmx_learn_lambda_slots", "rmx_learn_lambda_bind",
-    "rmx_learn_traces_clear", "rmx_learn_run",
+    "rmx_learn_traces_clear", "rmx_learn_run", "rmx_learn_eps_bind", "rmx_learn_eps_decay",
 )
 LEARN_UPDATE, LEARN_BEST, LEARN_NUMPY = 1, 2, 4  # RMX_LEARN_*
 LEARN_DYN_FIXED, LEARN_DYN_ENV = 0, 1  # rmx_learn_config.dynamics
@@ -61,7 +61,7 @@ HASHED_SOURCES = ("rmx_kernels.hip", "rmx_fast.hip", "rmx_fast_step.inc", "rmx_s
                   "rmx_comd.cpp", "rmx_build_info.cpp", "rmx_internal.h", "rmx_layout.h", "rmx_host.h", "rmx_device.h",
                   "rmx_generic.h", "rmx_comd.h", "rmx_hoststep.cpp", "rmx_hoststep.h", "rmx_learn.hip", "rmx_learn_run.hip", "rmx_learn.h",
                   "rmx_rules.h", "../../include/rmx.h",
-                  "Makefile")
+                  "Makefile", "rmx_learn_eps.hip", "rmx_learn_run_eps.hip")
 
 
 def source_hash(csrc: str = CSRC) -> str:
@@ -243,6 +243,8 @@ def load_library(path: str = None, check_source: bool = True):
         "rmx_learn_lambda_slots": (C.c_int, [vp, C.POINTER(C.c_int32)]),
         "rmx_learn_lambda_bind": (C.c_int, [vp, C.c_double, i32, vp, vp, vp]),
         "rmx_learn_traces_clear": (C.c_int, [vp, vp, vp]),
+        "rmx_learn_eps_bind": (C.c_int, [vp, vp, C.c_double, C.c_double]),
+        "rmx_learn_eps_decay": (C.c_int, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

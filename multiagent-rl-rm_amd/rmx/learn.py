@@ -13,6 +13,11 @@ the actions from the fresh start's rows, draws the slips and updates with the in
 reached, in the runner's order; the env's generator and the learners' own never mix.  Whole reference training runs
 on such worlds are reproduced bit for bit, the env's generator and episode count included (tests/golden/slearn_*.npz).
 
+Epsilon is the reference learner's own: with ``epsilon_start`` every learner has its entry in the ``[A, N]`` column
+``epsilon``, decayed as ``learn_done_episode`` decays it (``max(epsilon_end, epsilon * epsilon_decay)``) whenever a
+learn step auto-resets the learner's env, which is what both worlds' ``reset()`` do to every ``QLearning`` learner
+(include/rmx.h, "per-learner epsilon schedules"; tests/golden/eps_*.npz).  Without it a step takes one scalar epsilon.
+
 ``VecQLambda`` is the same for the reference's ``QLearningLambda`` (Watkins Q(lambda), replacing traces): the learn step
 then sweeps each learner's list of live traces instead of the reference's dense ``e_table`` (tests/golden/lambda_*.npz).
 """
@@ -33,16 +38,21 @@ class VecQLearning:
     the OfficeWorld runner ``done``.  ``policy_seeds`` (an int, or an ``[A, N]`` array of learner seeds) gives every
     learner the reference's own ``np.random.default_rng(seed)`` for ``act_step(reference_stream=True)``: ``rng`` is
     then the generator column ``[5, A, N]`` (include/rmx.h; an int64 tensor holding the uint64 words on a GPU env, a
-    uint64 array on a host env)."""
+    uint64 array on a host env).  ``epsilon_start`` gives every learner the reference's epsilon schedule: ``epsilon``
+    is then an ``[A, N]`` float64 tensor (array on a host env) filled with it and bound (rmx_learn_eps_bind),
+    ``epsilon_end`` defaults to ``epsilon_start`` and ``epsilon_decay`` to 1.0; ``act_step`` and ``run`` then take no
+    epsilon of their own.  The column may be overwritten per learner at any time (an epsilon sweep over the envs)."""
 
     def __init__(self, env, gamma, learning_rate=None, qtable_init=1.0, use_qrm=False, use_rsh=False,
-                 trunc_is_terminal=None, policy_seeds=None):
+                 trunc_is_terminal=None, policy_seeds=None, epsilon_start=None, epsilon_end=None, epsilon_decay=None):
         # argument checks before the tables are allocated (several GB on a GPU env)
         if learning_rate is not None and float(learning_rate) == 0.0:
             raise ValueError("learning_rate must be > 0, or None for 1 / visits")
         if use_rsh and not use_qrm:
             raise ValueError("use_rsh without use_qrm is not supported (rmx_learn_bind refuses it: the reference's "
                              "non-QRM shaping reads a label-keyed dict by index)")
+        if epsilon_start is None and (epsilon_end is not None or epsilon_decay is not None):
+            raise ValueError("epsilon_end / epsilon_decay need epsilon_start")
         self.env, self.lib = env, env.lib
         self.host = getattr(env, "device", None) == "cpu"
         tab = env.tables
@@ -89,9 +99,76 @@ class VecQLearning:
                 self.rng = env.torch.zeros((5, env.A, env.N), dtype=env.torch.int64, device=env.device)
             _capi.check(self.lib.rmx_learn_rng_bind(env._h, ptr(self.rng)), "rmx_learn_rng_bind")
             _capi.check(self.lib.rmx_learn_rng_seed(env._h, seeds.ctypes.data, self._stream()), "rmx_learn_rng_seed")
+        self.epsilon = self.epsilon_end = self.epsilon_decay = None
+        if epsilon_start is not None:
+            if self.host:
+                col = np.full((env.A, env.N), float(epsilon_start), np.float64)
+            else:
+                col = env.torch.full((env.A, env.N), float(epsilon_start), dtype=env.torch.float64, device=env.device)
+            self.bind_epsilon(col, float(epsilon_start) if epsilon_end is None else epsilon_end,
+                              1.0 if epsilon_decay is None else epsilon_decay)
 
     def _stream(self):
         return None if self.host else self.env._stream()
+
+    def bind_epsilon(self, col, end, decay):
+        """rmx_learn_eps_bind with the caller's own column: a contiguous float64 ``[A, N]`` array (host env) or tensor
+        on the engine's device, holding every learner's current epsilon.  ``end`` / ``decay``: the reference's
+        ``epsilon_end`` / ``epsilon_decay``.  ``act_step`` / ``run`` then take ``epsilon=None``."""
+        env = self.env
+        if self.host:
+            ok = isinstance(col, np.ndarray) and col.dtype == np.float64 and col.flags.c_contiguous and \
+                col.size == env.A * env.N
+            p = col.ctypes.data if ok else None
+        else:
+            t = env.torch
+            ok = t.is_tensor(col) and col.dtype is t.float64 and col.get_device() == env.device.index and \
+                col.is_contiguous() and col.numel() == env.A * env.N
+            p = col.data_ptr() if ok else None
+        if not ok:
+            raise ValueError(f"the epsilon column must be a contiguous float64 [A={env.A}, N={env.N}] "
+                             + ("array" if self.host else "tensor on the engine's device"))
+        _capi.check(self.lib.rmx_learn_eps_bind(env._h, p, float(end), float(decay)), "rmx_learn_eps_bind")
+        self.epsilon, self.epsilon_end, self.epsilon_decay = col, float(end), float(decay)
+
+    def unbind_epsilon(self):
+        """Back to one scalar ``epsilon`` per ``act_step`` / ``run`` call."""
+        _capi.check(self.lib.rmx_learn_eps_bind(self.env._h, None, 0.0, 0.0), "rmx_learn_eps_bind")
+        self.epsilon = self.epsilon_end = self.epsilon_decay = None
+
+    def learn_done_episode(self, mask=None):
+        """The reference's ``learn_done_episode`` for every learner of the masked envs ([N] bool / uint8; None: every
+        env): ``epsilon = max(epsilon_end, epsilon * epsilon_decay)``, in stream order (rmx_learn_eps_decay).  The
+        learn steps do this themselves at their auto-resets; this serves the resets a loop makes before its first step
+        (``env.reset`` leaves the column alone)."""
+        _capi.check(self.lib.rmx_learn_eps_decay(self.env._h, self._mask_ptr(mask), self._stream()),
+                    "rmx_learn_eps_decay")
+
+    def _mask_ptr(self, mask):
+        """An [N] env mask as the pointer the ABI takes (None: NULL); the array stays alive in ``self._mask``."""
+        env = self.env
+        if mask is None:
+            return None
+        if self.host:
+            m = np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
+            p = m.ctypes.data
+        else:
+            m = env.torch.as_tensor(mask).to(device=env.device, dtype=env.torch.uint8).contiguous()
+            p = m.data_ptr()
+        if (m.size if self.host else m.numel()) != env.N:
+            raise ValueError(f"mask must be [N={env.N}]")
+        self._mask = m  # (a device mask is read in stream order, as env.reset's)
+        return p
+
+    def _epsilon_arg(self, epsilon):
+        """The scalar the ABI validates: the caller's, or with a schedule bound (where it must be None) 0."""
+        if self.epsilon is not None:
+            if epsilon is not None:
+                raise ValueError("an epsilon schedule is bound (epsilon_start / bind_epsilon): epsilon must be None")
+            return 0.0
+        if epsilon is None:
+            raise ValueError("epsilon is required (no epsilon schedule is bound)")
+        return float(epsilon)
 
     def step(self, actions, autoreset=True):
         """One wrapper step with the caller's actions ([A, N] int32, 0..3) and every learner's update."""
@@ -109,13 +186,16 @@ class VecQLearning:
             p = a.data_ptr()
         _capi.check(self.lib.rmx_learn_step(env._h, p, 1 if autoreset else 0, self._stream()), "rmx_learn_step")
 
-    def act_step(self, epsilon, seed=None, t_global=None, best=False, learn=True, autoreset=True, actions_out=None,
+    def act_step(self, epsilon=None, seed=None, t_global=None, best=False, learn=True, autoreset=True, actions_out=None,
                  reference_stream=False):
         """One step with the engine's policy (epsilon-greedy over each learner's own row with hash-chosen ties;
         ``best``: np.argmax), and with ``learn`` the update.  ``actions_out``: an [A, N] int32 array / tensor that
         receives the chosen actions.  ``reference_stream``: the reference's ``choose_action`` on each learner's own
-        numpy generator instead (``policy_seeds``); ``seed`` and ``t_global`` are then unused and may be ``None``."""
+        numpy generator instead (``policy_seeds``); ``seed`` and ``t_global`` are then unused and may be ``None``.
+        ``epsilon``: the scalar every learner explores under; ``None`` (and only ``None``) with an epsilon schedule
+        bound, where each learner has its own and the step decays it at its env's auto-reset."""
         env = self.env
+        epsilon = self._epsilon_arg(epsilon)
         if reference_stream:
             if self.rng is None:
                 raise RuntimeError("act_step(reference_stream=True) needs policy_seeds at construction")
@@ -139,7 +219,7 @@ class VecQLearning:
                     "rmx_learn_step_policy")
         return actions_out
 
-    def run(self, T, epsilon, seed=None, t_global=None, best=False, learn=True, reference_stream=False,
+    def run(self, T, epsilon=None, seed=None, t_global=None, best=False, learn=True, reference_stream=False,
             actions_out=None):
         """``T`` consecutive auto-resetting ``act_step``s (global steps ``t_global .. t_global + T - 1``) in one
         launch on a GPU env (rmx_learn_run; csrc/rmx_learn_run.hip): the tables, every column, the generators and the
@@ -149,8 +229,10 @@ class VecQLearning:
         into consecutive calls.  A run pays one launch and one Python call for T steps and touches the state and
         output columns once: at config 2 with QRM a step inside run(1000) takes 0.63 of a step called on its own at
         64 envs, 0.70 at 4,096 and 0.73 at 65,536 (profiles/learn_run.md; worlds of five or more agents have not been
-        timed)."""
+        timed).  ``epsilon`` as in ``act_step``: with a schedule bound every env anneals at its own resets inside the
+        launch."""
         env = self.env
+        epsilon = self._epsilon_arg(epsilon)
         T = int(T)
         if T < 1:
             raise ValueError("T must be >= 1")
@@ -242,12 +324,16 @@ class VecQLambda(VecQLearning):
     (default: ``4 * S_max``, which cannot overflow) is L; a trace that finds its list full is dropped and
     ``env.check_errors()`` raises ``RuntimeError``.  Steps taken through the env's own ``step`` / ``step_seq`` /
     ``rollout`` leave the lists alone, their auto-resets included: call ``clear_traces`` when mixing them in.
-    Not reproduced: an explicit ``next_action``, softmax action selection, epsilon decay."""
+    The reference's ``reset()`` does not call ``learn_done_episode`` on a ``QLearningLambda`` (it is no ``QLearning``),
+    so its runners keep epsilon fixed: leave ``epsilon_start`` unset for them.  The class has a ``learn_done_episode``
+    of its own; a loop that calls it at every reset is what ``epsilon_start`` / ``epsilon_end`` / ``epsilon_decay``
+    reproduce here.  Not reproduced: an explicit ``next_action``, softmax action selection."""
 
     def __init__(self, env, gamma, lambd, learning_rate=None, qtable_init=0.0, trunc_is_terminal=None,
-                 policy_seeds=None, trace_cap=None):
+                 policy_seeds=None, trace_cap=None, epsilon_start=None, epsilon_end=None, epsilon_decay=None):
         super().__init__(env, gamma, learning_rate, qtable_init=qtable_init, use_qrm=False, use_rsh=False,
-                         trunc_is_terminal=trunc_is_terminal, policy_seeds=policy_seeds)
+                         trunc_is_terminal=trunc_is_terminal, policy_seeds=policy_seeds, epsilon_start=epsilon_start,
+                         epsilon_end=epsilon_end, epsilon_decay=epsilon_decay)
         full = C.c_int32()
         _capi.check(self.lib.rmx_learn_lambda_slots(env._h, C.byref(full)), "rmx_learn_lambda_slots")
         self.trace_full = int(full.value)
@@ -300,16 +386,5 @@ class VecQLambda(VecQLearning):
 
     def clear_traces(self, mask=None):
         """Empty the lists of the masked envs ([N] bool / uint8; None: every env)."""
-        env = self.env
-        p = None
-        if mask is not None:
-            if self.host:
-                m = np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
-                p = m.ctypes.data
-            else:
-                m = env.torch.as_tensor(mask).to(device=env.device, dtype=env.torch.uint8).contiguous()
-                p = m.data_ptr()
-            if (m.size if self.host else m.numel()) != env.N:
-                raise ValueError(f"mask must be [N={env.N}]")
-        # (a device mask is read in stream order, as env.reset's)
-        _capi.check(self.lib.rmx_learn_traces_clear(env._h, p, self._stream()), "rmx_learn_traces_clear")
+        _capi.check(self.lib.rmx_learn_traces_clear(self.env._h, self._mask_ptr(mask), self._stream()),
+                    "rmx_learn_traces_clear")
