@@ -269,6 +269,15 @@ int rmx_step_report_fused(const rmx_handle* h);
  * hold after the call exactly what the n_steps calls would have left.  A failed window leaves them undefined, as
  * before.  The default deterministic step (no slip, fixed starts, no QRM outputs, below 1M envs) takes this form for
  * n_steps >= 2; RMX_SEQ_PACKED=0 in the environment at rmx_create keeps the window of n_steps column-to-column steps.
+ * Fences: every packet of a window waits for the one before it (barrier bit) and starts with an agent-scope acquire.
+ * The packets of a packed window before its last end with NO release fence: all they leave behind is the handle's
+ * private record and its statistics slots, written with write-through stores and agent-scope atomics that each wave
+ * waits for before it ends.  The last packet of a packed window, every packet of an unpacked one and a window of one
+ * step end with an agent-scope release.  RMX_SEQ_RELEASE=1 in the environment at rmx_create keeps the release on
+ * every packet (results are the same; the switch is for measurements and as a fallback).
+ * rmx_seq_handoff(k, n_steps, packed, release_all): 1 if packet k of an n_steps window is recorded as such a private
+ * hand-off (no release fence), for a packed / unpacked window and RMX_SEQ_RELEASE set / unset; a pure function, the
+ * rule rmx_step_seq's recording applies.
  * rmx_queue_counters: that queue's windows, kernel-argument uploads and packets so far for the handle's device.
  * rmx_queue_info: out[0..n) of RMX_QUEUE_INFO_N values: [0] windows, [1] uploads, [2] packets (as above), [3] windows
  * of the device served on a stream, [4] the device queue's state (RMX_QUEUE_*), [5] how the handle's last
@@ -278,6 +287,7 @@ int rmx_step_seq(rmx_handle* h, const int32_t* actions_dev, int64_t action_strid
                  double* stats_out_dev, void* hip_stream);
 /* 1 if the handle's last rmx_step_seq ran on the queue as a packed window (the private layout above), else 0. */
 int rmx_seq_packed(const rmx_handle* h);
+int rmx_seq_handoff(int32_t k, int32_t n_steps, int packed, int release_all);
 int rmx_queue_counters(const rmx_handle* h, int64_t* out3);
 #define RMX_QUEUE_INFO_N 7
 #define RMX_QUEUE_UNUSED 0      /* not set up yet (no window on this device so far) */

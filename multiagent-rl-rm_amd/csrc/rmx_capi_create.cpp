@@ -75,6 +75,7 @@ struct CreateTables {
 static void create_env(rmx_handle* h, const rmx_config* cfg) {
   if (const char* qv = std::getenv("RMX_QUEUE")) h->seq.queue_off = std::strcmp(qv, "0") == 0;
   if (const char* pv = std::getenv("RMX_SEQ_PACKED")) h->seq.packed_off = std::strcmp(pv, "0") == 0;
+  if (const char* rv = std::getenv("RMX_SEQ_RELEASE")) h->seq.release_all = std::strcmp(rv, "1") == 0;
   if (const char* b = std::getenv("RMX_BLOCK")) {
     int v = std::atoi(b);
     if (v == 64 || v == 128 || v == 256) h->block = v;

@@ -52,6 +52,9 @@ static bool record_seq(rmx_handle* h, const int32_t* actions, int64_t stride, in
     if (!cap.ok) return false;
     // the kernel side's dispatch must have taken the window kernel: a mixed window would read columns nobody wrote
     if (packed && !std::strstr(h->seq.window[(size_t)k].symbol, "step_fast_kernel_win")) return false;
+    // packets 0 .. K - 2 of a packed window leave only the handle's record and statistics slots behind, all written
+    // through: no release fence (queue_run); the last packet, which writes the caller's columns, keeps both fences
+    h->seq.window[(size_t)k].handoff = rmx::seq_handoff(k, K, packed, h->seq.release_all) ? 1u : 0u;
   }
   return true;
 }
@@ -158,6 +161,10 @@ int rmx_step_seq(rmx_handle* h, const int32_t* actions_dev, int64_t action_strid
 
 int rmx_seq_packed(const rmx_handle* h) {
   return h && !h->host && h->seq.dispatch == RMX_SEQ_QUEUE && h->seq.key && h->seq.is_packed ? 1 : 0;
+}
+
+int rmx_seq_handoff(int32_t k, int32_t n_steps, int packed, int release_all) {
+  return rmx::seq_handoff(k, n_steps, packed != 0, release_all != 0) ? 1 : 0;
 }
 
 int rmx_queue_counters(const rmx_handle* h, int64_t* out3) {

@@ -756,6 +756,13 @@ __device__ __forceinline__ void rs_step(const FastParams& p, Pcg& rng, int32_t& 
 // body, so a window cannot compute anything else than its steps one by one.
 // (the body itself: rmx_fast_step.inc, included into both kernels below)
 
+// Window packets that read the record take its pointer from a preloaded argument slot from this many agents on
+// (rmx_fast_step.inc PK_PRE; below it, from the parameter block).  Measured per interior dispatch, release fences
+// on, three alternated runs each (profiles/r08_window_handoff.md §1): config 4 (A = 4) 2.99 -> 2.83 us at K = 20 and
+// 3.51 -> 3.13 us at K = 500; config 2 (A = 2) 2.34 -> 2.31 us at K = 20 but 2.49 -> 2.54 us at K = 500 (slower than
+// the parent in every run, as round 1 found for step_fast_kernel's preload with cold actions), so A <= 2 stays off.
+constexpr int kWinPreMinA = 3;
+
 template <int KIND, int A, bool HASHED, int TBL, int QXB = 0, int SKIP = kSkipNone, bool RPT = false,
           int SLIP = 0>
 __global__ void __launch_bounds__(256) step_fast_kernel(int32_t N_arg, int32_t blk_arg, const int32_t* x_arg,
@@ -1082,6 +1089,14 @@ thread_local StepCapture* tl_capture = nullptr;
 static StepArgs step_args(const FastParams& p, uint32_t blk) {
   return StepArgs{p.N, (int32_t)blk, p.pos_x, p.pos_y, p.rm_q, p.flags, p.t, p.actions, p};
 }
+// step_fast_kernel_win's: a packet that reads the record (kIoPkToPk, kIoPkToCols) never reads the columns, so its
+// first preloaded pointer slot carries the record buffer instead of pos_x: the record loads issue at wave start
+// (rmx_fast_step.inc PRE && IN_PK).  The parameter list and the symbol spelling are step_args'.
+static StepArgs step_args_win(const FastParams& p, uint32_t blk, int io) {
+  StepArgs a = step_args(p, blk);
+  if (io == kIoPkToPk || io == kIoPkToCols) a.pos_x = reinterpret_cast<const int32_t*>(p.pk);
+  return a;
+}
 
 // Every step_fast_kernel launch: issued on st, or, under a StepCapture (rmx_step_seq), recorded for the engine's own
 // queue with the instantiation's code-object symbol (its Itanium mangling: the eight template arguments, then the
@@ -1092,6 +1107,7 @@ static void capture_launch(StepCapture* c, dim3 g, dim3 b, size_t lds, const Ste
   L.grid = g.x;
   L.block = b.x;
   L.lds = (uint32_t)lds;
+  L.handoff = 0;  // (the window's recorder decides: rmx_capi_seq.cpp record_seq)
   // byte copies (padding included: the host compares consecutive windows' kernargs byte for byte)
   std::memset(&L.args, 0, sizeof(L.args));
   std::memcpy(&L.args, &a, offsetof(StepArgs, p));
@@ -1117,7 +1133,7 @@ static void go_step(dim3 g, dim3 b, size_t lds, hipStream_t st, const FastParams
 // symbol.  Only rmx_step_seq's recording asks for these; outside a capture the launch is issued like any other.
 template <int KIND, int A, int TBL, bool RPT, int IO>
 static void go_step_win(dim3 g, dim3 b, hipStream_t st, const FastParams& p) {
-  const StepArgs a = step_args(p, b.x);
+  const StepArgs a = step_args_win(p, b.x, IO);
   if (StepCapture* c = tl_capture) {
     snprintf(c->out->symbol, sizeof(c->out->symbol),
              "_ZN3rmx20step_fast_kernel_winILi%dELi%dELi%dELb%dELi%dEEEviiPKiS2_S2_PKjS2_S2_NS_10FastParamsE.kd", KIND, A,

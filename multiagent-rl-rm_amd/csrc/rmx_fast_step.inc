@@ -39,7 +39,12 @@
   // Preloaded pointers for A >= 3 only: measured (r01_ab_log c80) 9-11 % faster for configs 4 and 5, while for
   // A <= 2 the early load burst made config 2 bimodal (3.11 or 3.55-3.77 us per step with cold actions, vs a
   // steady 3.35-3.40) and config 3 3 % slower; there the kernarg-fetched FastParams pointers are used.
-  constexpr bool PRE = A >= 3;
+  // Window packets that read the record (IN_PK) take its pointer from the first preloaded slot (x_arg: go_step_win
+  // passes p.pk there, these packets never read the columns) for A >= kWinPreMinA, so the record loads issue at wave
+  // start as the column loads do here; below that they fetch p.pk from the parameter block like every other pointer
+  // (kWinPreMinA and its measurements: rmx_fast.hip).
+  constexpr bool PK_PRE = IN_PK && A >= kWinPreMinA;
+  constexpr bool PRE = A >= 3 || PK_PRE;
   const int32_t N = PRE ? N_arg : p.N;
 #ifdef RMX_DIAG
   // diag 65536: XCD-contiguous env ranges (workgroups are dealt round-robin to the 8 XCDs: give XCD x the
@@ -55,7 +60,8 @@
   const uint32_t off = (uint32_t)e * 4u;
   const uint32_t col = (uint32_t)N * 4u;  // bytes per agent column (A*N*4 < 2^31 on the fast path)
   const uint32_t cols = col * (uint32_t)A;
-  const auto r_x = col_rsrc(PRE ? x_arg : p.pos_x, cols), r_y = col_rsrc(PRE ? y_arg : p.pos_y, cols);
+  // (with PK_PRE the x_arg slot holds the record: the last packet's pos_x stores take the column from the block)
+  const auto r_x = col_rsrc(PRE && !PK_PRE ? x_arg : p.pos_x, cols), r_y = col_rsrc(PRE ? y_arg : p.pos_y, cols);
   const auto r_q = col_rsrc(PRE ? q_arg : p.rm_q, cols), r_f = col_rsrc(PRE ? f_arg : p.flags, cols);
   const auto r_t = col_rsrc(PRE ? t_arg : p.t, col);
   const auto r_act = col_rsrc(PRE ? act_arg : p.actions, cols), r_rew = col_rsrc(p.reward, cols);
@@ -66,10 +72,11 @@
   if constexpr (!IN_PK) t = col_ld(r_t, off, 0);
   __amdgpu_buffer_rsrc_t r_ret;  // built after the preloaded-pointer loads are issued (it needs a kernarg fetch)
   // the window's packed record (rmx_layout.h): [3A + 1][N] words of the handle's buffer
-  [[maybe_unused]] const auto r_pk = col_rsrc(p.pk, IO != kIoCols ? col * (uint32_t)(3 * A + 1) : 0u);
+  [[maybe_unused]] const auto r_pk =
+      col_rsrc(PK_PRE ? (const void*)x_arg : (const void*)p.pk, IO != kIoCols ? col * (uint32_t)(3 * A + 1) : 0u);
   if constexpr (IN_PK) {
     t = col_ld(r_pk, off, (uint32_t)pk_col_t(A) * col);
-    r_ret = col_rsrc(p.ep_ret, cols);
+    if constexpr (!PK_PRE) r_ret = col_rsrc(p.ep_ret, cols);
 #pragma unroll
     for (int a = 0; a < A; ++a) {
       const uint32_t cw = (uint32_t)col_ld(r_pk, off, (uint32_t)pk_col_cell(A, a) * col);
@@ -80,6 +87,10 @@
       s[a].ret = __int_as_float(col_ld(r_pk, off, (uint32_t)pk_col_ret(A, a) * col));
       s[a].act = col_ld(r_act, off, a * col);
       s0[a] = s[a];
+    }
+    if constexpr (PK_PRE) {  // as below: nothing that needs a kernarg fetch above the record loads
+      __builtin_amdgcn_sched_barrier(0);
+      r_ret = col_rsrc(p.ep_ret, cols);
     }
   } else if constexpr (!PRE) {
     r_ret = col_rsrc(p.ep_ret, cols);
@@ -411,6 +422,16 @@
   // slower, so those keep the atomics last.
   if constexpr (STATS_FIRST) flush_stats();
   STAMP(6);
+  // What a packet with OUT_PK leaves behind is read by the next packet of its window without a release fence in
+  // between (rmx_queue.cpp queue_run), so every byte of it must be written through: the record's words by st() with
+  // sc1, the statistics slots and the error word by agent-scope atomics (flush_stats with per-env slots, atomicOr).
+  // Audit of the default-policy stores of this body: byte_st, the optional columns (shaping, renv, enc_state) and the
+  // rng columns sit in the `else` of `if constexpr (OUT_PK)` below; the QRM stores need QXB > 0 and the report RPT:
+  // all compiled out of these packets (the assertions here and at the top).  The per-wave slab slot's plain store
+  // (p.wave_stats, a run-time switch) is never reached: launch_tpe_t dispatches a window kernel only with
+  // !p.wave_stats, and rmx_step_seq packs only handles with per-env slots (seq_packs).
+  static_assert(!OUT_PK || (SAUX == kStoreAux && !QRM && !RNG && !RPT && IO != kIoCols),
+                "a hand-off packet stores through st() with sc1 and through agent-scope atomics only");
   if constexpr (OUT_PK) {
     // the record only: x, y and rm_q are table bytes here (rmx_layout.h); the window's first step writes every word
     // (the buffer holds another window's records), later ones ep_ret only where it changed
@@ -564,3 +585,6 @@
     }
     report_tail(p, rin, done, rs, sc, t1);
   }
+  // A hand-off packet has no release fence behind it: each storing wave waits here until its record stores and its
+  // atomics have completed (gfx9: stores count in vmcnt), so they are in memory when the last wave has ended.
+  if constexpr (OUT_PK) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

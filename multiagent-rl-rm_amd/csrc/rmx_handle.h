@@ -31,6 +31,8 @@ struct rmx_handle {
     // packed windows (rmx_layout.h "the packed record"): RMX_SEQ_PACKED=0 at rmx_create turns them off; the record
     // buffer is allocated by the first eligible window (a failed allocation is remembered: windows stay unpacked)
     bool packed_off = false;
+    // RMX_SEQ_RELEASE=1 at rmx_create: every packet of a packed window keeps its release fence (rmx::seq_handoff)
+    bool release_all = false;
     bool pk_failed = false;
     bool pk_refused = false;  // the kernel side did not take the window kernel for this handle: not tried again
     uint32_t* d_pk = nullptr;

@@ -261,11 +261,19 @@ struct StepArgs {
 };
 static_assert(sizeof(StepArgs) == 56 + sizeof(FastParams), "step_fast_kernel's parameter list: no padding");
 // one step launch recorded instead of issued: the instantiation's code-object symbol, 1-D geometry, dynamic LDS
+// handoff: this packet's outputs are private to its window and written through (a packed window's packets before the
+// last, seq_handoff): the queue gives it no release fence (rmx_queue.cpp queue_run has the argument)
 struct StepLaunch {
   char symbol[160];
   uint32_t grid, block, lds;
+  uint32_t handoff;
   StepArgs args;
 };
+// Which packets of a K-packet window are private hand-offs: packets 0 .. K - 2 of a packed window; none of an unpacked
+// window or of K = 1, and none with RMX_SEQ_RELEASE=1 (release_all).  The one rule for record_seq and rmx_seq_handoff.
+constexpr bool seq_handoff(int32_t k, int32_t K, bool packed, bool release_all) {
+  return packed && !release_all && K >= 2 && k >= 0 && k < K - 1;
+}
 // While tl_capture is set, launch_step_fast records the launch into *out (ok = true) instead of issuing it; a handle
 // whose step is not the thread-per-env step_fast_kernel records nothing (ok stays false) and launches nothing.
 struct StepCapture {

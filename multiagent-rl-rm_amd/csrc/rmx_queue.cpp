@@ -95,6 +95,7 @@ struct DeviceQueue {
   // the previous window's packets (bodies without the header word) under its key
   uint64_t last_key = 0;
   std::vector<hsa_kernel_dispatch_packet_t> built;
+  std::vector<unsigned char> built_handoff;  // per packet of `built`: StepLaunch::handoff (no release fence)
   int64_t windows = 0, uploads = 0, packets = 0, stream_windows = 0;
   // dispatch timing: the stride (0 off), one signal per stamped packet, the last timed window's stamps
   int timing = 0;
@@ -306,7 +307,9 @@ int build_window(DeviceQueue& d, const StepLaunch* L, int K, std::string* err) {
     ++d.uploads;
   }
   d.built.assign((size_t)K, hsa_kernel_dispatch_packet_t{});
+  d.built_handoff.assign((size_t)K, 0);
   for (int i = 0; i < K; ++i) {
+    d.built_handoff[(size_t)i] = L[i].handoff ? 1 : 0;  // with the cached window: a reused recording keeps it
     hsa_kernel_dispatch_packet_t& pk = d.built[(size_t)i];
     pk.workgroup_size_x = (uint16_t)L[i].block;
     pk.workgroup_size_y = 1;
@@ -370,6 +373,15 @@ int queue_run(int device, const StepLaunch* L, int K, uint64_t key, std::string*
   // dirty lines back to the memory side after it (where the other XCDs, copy engines and the host's copies read) —
   // what the window needs for device-memory inputs written by earlier kernels or copies and outputs read after it.
   // System scope (host-coherent memory) cost ~4 us more per window (profiles/r04_ab_log.md aql).
+  // A hand-off packet (StepLaunch::handoff: packets 0 .. K - 2 of a packed window) carries no release fence.  What the
+  // next packet reads of it is the handle's record and statistics slots, and
+  //  - every such byte is written by an sc1 (write-through) store or an agent-scope atomic (rmx_fast_step.inc, the
+  //    audit above `if constexpr (OUT_PK)`): neither leaves a dirty line in an L2 for a release to write back;
+  //  - every storing wave has waited for them (its closing s_waitcnt vmcnt(0)), so they are complete when it ends;
+  //  - the barrier bit starts the next dispatch only after all waves of this one have ended;
+  //  - the next packet's agent-scope acquire invalidates the L1s, the scalar caches and the L2s before any of its loads.
+  // Nothing here depends on which XCD runs which workgroup or on which lines a write-through store evicts.  The
+  // acquire stays on every packet, and the window's last packet (the caller's columns) keeps both fences.
   hsa_queue_t* q = d.q;
   const uint64_t size = q->size;
   // dispatch timing: packets 0, m, 2m, ... (m = d.timing) get completion signals of their own, the last one keeps
@@ -430,10 +442,11 @@ int queue_run(int device, const StepLaunch* L, int K, uint64_t key, std::string*
     std::memcpy(reinterpret_cast<char*>(pk) + 4, reinterpret_cast<const char*>(&b) + 4, sizeof(b) - 4);
     pk->completion_signal = i == K - 1 ? d.done : n_timed && sig_of[(size_t)i] >= 0 ? d.tsig[(size_t)sig_of[(size_t)i]]
                                                                                    : hsa_signal_t{0};
+    const int release = d.built_handoff[(size_t)i] && i + 1 < K ? HSA_FENCE_SCOPE_NONE : HSA_FENCE_SCOPE_AGENT;
     const uint16_t header = (uint16_t)((HSA_PACKET_TYPE_KERNEL_DISPATCH << HSA_PACKET_HEADER_TYPE) |
                                        (1 << HSA_PACKET_HEADER_BARRIER) |
                                        (HSA_FENCE_SCOPE_AGENT << HSA_PACKET_HEADER_SCACQUIRE_FENCE_SCOPE) |
-                                       (HSA_FENCE_SCOPE_AGENT << HSA_PACKET_HEADER_SCRELEASE_FENCE_SCOPE));
+                                       (release << HSA_PACKET_HEADER_SCRELEASE_FENCE_SCOPE));
     const uint16_t setup = 1 << HSA_KERNEL_DISPATCH_PACKET_SETUP_DIMENSIONS;
     __atomic_store_n(reinterpret_cast<uint32_t*>(pk), (uint32_t)header | ((uint32_t)setup << 16), __ATOMIC_RELEASE);
     ++d.packets;

@@ -28,8 +28,9 @@ EXPORTS = (
     "rmx_get_state", "rmx_set_state", "rmx_step_report", "rmx_step_report_fused", "rmx_reset_sync", "rmx_step_sync",
     "rmx_step_sync_begin", "rmx_sync_wait", "rmx_sync_end", "rmx_step_seq", "rmx_queue_counters", "rmx_queue_info",
     "rmx_code_object_check", "rmx_device_count", "rmx_queue_timing", "rmx_queue_times", "rmx_step_info",
-    "rmx_seq_packed", "rmx_learn_states", "rmx_learn_bind", "rmx_learn_step", "rmx_learn_step_policy",
-    "rmx_learn_rng_bind", "rmx_learn_rng_seed", "rmx_learn_lambda_slots", "rmx_learn_lambda_bind",
+    "rmx_seq_packed", "rmx_seq_handoff", "rmx_learn_states", "rmx_learn_bind", "rmx_learn_step",
+    "rmx_learn_step_policy", "rmx_learn_rng_bind", "rmx_learn_rng_seed", "rmx_learn_lambda_slots",
+    "rmx_learn_lambda_bind",
     "rmx_learn_traces_clear", "rmx_learn_run", "rmx_learn_eps_bind", "rmx_learn_eps_decay",
 )
 LEARN_UPDATE, LEARN_BEST, LEARN_NUMPY = 1, 2, 4  # RMX_LEARN_*
@@ -218,6 +219,7 @@ def load_library(path: str = None, check_source: bool = True):
         "rmx_step_report": (C.c_int, [vp, vp, C.c_int, vp, vp]),
         "rmx_step_report_fused": (C.c_int, [vp]),
         "rmx_seq_packed": (C.c_int, [vp]),
+        "rmx_seq_handoff": (C.c_int, [C.c_int32, C.c_int32, C.c_int, C.c_int]),
         "rmx_step_seq": (C.c_int, [vp, vp, C.c_int64, C.c_int32, C.c_int, vp, vp]),
         "rmx_queue_timing": (C.c_int, [vp, C.c_int]),
         "rmx_queue_times": (C.c_int, [vp, vp, C.c_int64, C.POINTER(C.c_int64)]),

@@ -5,8 +5,8 @@ one doorbell, each packet behind the previous one), after a 1-s spin-up.  Run un
     rocprofv3 --kernel-trace --stats -- python3 scripts/trace_window.py --config 2 --k 500 --windows 20
 the tracer sees K dependent dispatches submitted together, so each starts as the previous ends (not on an idle GPU, as
 eager launches under the tracer do: profiles/r05_ab_log.md trace).  Prints one JSON line: the wall-clock time per step
-of the same windows (host clock around each blocking rmx_step_seq, median), to set beside the trace's per-dispatch
-durations (scripts/summarize_trace.py).
+of the same windows (host clock around each blocking rmx_step_seq: median, min, max and every window's value), to set
+beside the trace's per-dispatch durations (scripts/summarize_trace.py).
 """
 import argparse
 import json
@@ -52,7 +52,9 @@ def main():
     q = env.queue_info()
     print(json.dumps({"config": args.config, "n_envs": args.n_envs, "k": args.k, "windows": args.windows,
                       "spin_windows": spins, "us_per_step_wall_median": statistics.median(walls),
-                      "us_per_step_wall_min": min(walls), "dispatch": q["dispatch"], "queue_state": q["state"],
+                      "us_per_step_wall_min": min(walls), "us_per_step_wall_max": max(walls),
+                      "us_per_step_wall": [round(w, 4) for w in walls],  # every window: the spread, two modes if any
+                      "dispatch": q["dispatch"], "queue_state": q["state"],
                       "kernel": "rmx::step_fast_kernel"}), flush=True)
 
 
