@@ -54,6 +54,7 @@ extern "C" {
 #define RMX_E_ACTION (-3)   /* an action outside [0,4] was seen  -> ValueError            */
 #define RMX_E_STATE (-4)    /* buffers not bound / wrong sizes   -> RuntimeError          */
 #define RMX_E_TRACE (-5)    /* a Q(lambda) trace list was full   -> RuntimeError          */
+#define RMX_E_MODEL (-6)    /* an R-max successor list was full  -> RuntimeError          */
 
 #define RMX_DEVICE_HOST (-1) /* rmx_config.device: the host path (no GPU) */
 
@@ -594,6 +595,73 @@ int rmx_learn_traces_clear(rmx_handle* h, const uint8_t* env_mask_dev, void* hip
  * before any device work. */
 int rmx_learn_eps_bind(rmx_handle* h, double* eps /* [A][N]; NULL unbinds */, double eps_end, double eps_decay);
 int rmx_learn_eps_decay(rmx_handle* h, const uint8_t* env_mask /* NULL: all */, void* hip_stream);
+
+/* ---- R-max learners: a learned model per learner, solved by value iteration ----------------------------------
+ * RMax (learning_algorithms/rmax.py) behind AgentRL.update_policy, as the OfficeWorld runner builds it for
+ * --algorithm RMAX / RMAXRM (office_main.py:663-684): one learner per (agent a, env e).  rmx_learn_bind comes first: q
+ * is filled by the caller with max_reward/(1 - gamma), the visits table serves as s_a_counts and is required, use_rsh
+ * is refused, learning_rate is unused.  rmx_learn_rmax_bind then turns the handle's learners into R-max ones;
+ * rmx_learn_step and rmx_learn_step_policy run the R-max learn step (a device handle: at most two launches on the
+ * caller's stream, rmx_learn_rmax.hip; no device synchronisation).  State encoding, the experiences of one agent-step
+ * and the done rule (trunc_is_terminal) are those of the Q-learning section.
+ * Caller-owned arrays beside q and visits, learner-major (a solve reads one learner's together):
+ *   rsum float64 [A][N][S_max][4] (the reference's `rewards`), succ_idx / succ_cnt int32 [A][N][S_max][4][cap]: the
+ *   non-zero entries of the reference's dense transitions[s][k][:] as a list, slot j of pair (s, k) of learner (a, e)
+ *   at ((((a*N + e)*S_max + s)*4 + k)*cap + j; a slot with succ_cnt == 0 is empty; slots fill in first-seen order.
+ *   The caller zeroes all three.
+ * One update_q(s, k, r, sn, done), rmax.py:156-170, in this order:
+ *   done: q[sn][0..3] = 0, the lists of (sn, 0..3) become the single entry (sn, threshold), counts[sn][0..3] =
+ *         threshold; rsum[sn] is left alone; this triggers no solve;
+ *   counts[s][k] < threshold: rsum[s][k] += r (one float64 add); counts[s][k] += 1; the count of successor sn in the
+ *         list of (s, k) += 1 (appended with count 1 if new); if counts[s][k] == threshold now, the learned MDP is
+ *         solved at once, before the next experience of the same step.
+ * Experiences of one agent-step: the real one first (r = (double)Renv + (double)reward_modifier*(double)RQ, the
+ * intended action), then with use_qrm every counterfactual in get_all_states()[:-1] order (r = (double)Renv +
+ * (double)rq_j), the RM state actually held included once more: the reference double counts it, and so does the
+ * engine.  An action without a table column, or an experience with s or sn outside the agent's rows, is dropped.
+ * Value iteration (rmax.py:185-227) over mask = counts >= threshold, at most max_iter sweeps (the reference: 10000):
+ *   v[n] = max(q[n][0..3]);  for every masked (s, k): new = rsum/counts + gamma * sum_slots (cnt_slot/counts)*v[idx],
+ *   the sum in slot order from +0.0, each step one IEEE float64 operation, never fused;  the sweep has converged when
+ *   |q - new| < vi_delta for every masked entry (vi_delta_rel: the difference divided by |q| where q != 0, taken as 0
+ *   where q == 0), tested before anything is written;  otherwise q[mask] = new[mask], a Jacobi sweep.  Unmasked
+ *   entries are never written by a solve.
+ * Bit-exactness: the dense transitions row is non-zero exactly for the listed successors, and adding 0.0 changes no
+ * float64 but -0.0, so the dense einsum over n is a sum of the listed terms; a sum of at most two of them does not
+ * depend on the order, so on worlds where every (s, k) has at most two successors q equals the reference's bit for
+ * bit, as counts, rsum and the lists always do.  With three or more successors numpy's einsum sums in another order:
+ * q then agrees within 2*vi_delta/(1 - gamma) (both stop at a Bellman residual below vi_delta on the same model).
+ * Policy (rmax.py:108-128): there is no epsilon; rmx_learn_step_policy validates its scalar and ignores it, and a
+ * bound epsilon column is left alone (never read, never decayed).  A row whose four entries equal row[0] (float64
+ * equality), unless RMX_LEARN_BEST: rng.choice of the four actions, which is integers(0, 4) on the learner's own
+ * generator under RMX_LEARN_NUMPY (no other draw is made, and a row that is not flat draws nothing) and h0 >> 62 of
+ * the engine's hashed policy otherwise.  Any other row, and every row under RMX_LEARN_BEST: the first maximum.  A
+ * state outside the agent's rows reads as four zeros, which is therefore the random case.
+ * Capacity: rmx_learn_rmax_slots() = 5 can never overflow.  The derivation, from agent_step (csrc/rmx_rules.h): the
+ * cell after an agent-step is the agent's own or one of its four neighbours, whatever the slip outcome (a slip only
+ * replaces the direction; a blocked move, a wall collision and a frozen agent stay put; a hole or a plant is entered
+ * like any cell), so at most five cells; the next RM index is next_q[q][event(cell')] for the real experience and
+ * for every counterfactual alike (a frozen agent's RM still steps on its own cell), a function of (q, cell'); other
+ * agents never move or block an agent.  So sn is a function of (s, cell'), and (s, k) has at most five successors;
+ * a deterministic world has one.  A caller may bind fewer.  A successor that finds its list full is still counted in
+ * counts and rsum, its list entry is dropped, and the error word gets a bit that rmx_check_errors reports as
+ * RMX_E_MODEL (an invalid action or a full trace list reported at the same time wins).  Nothing is written at or past
+ * slot cap.
+ * None of the arrays is part of rmx_get_state, and no reset touches them: env.reset() does nothing to an RMax.
+ * rmx_learn_run on a handle with R-max bound: RMX_E_STATE (one thread per env cannot run a workgroup-wide solve); a
+ * caller loops rmx_learn_step_policy.  A device handle keeps the values of the learner being solved in LDS, 16 B per
+ * state: S_max above 4064 is refused at bind (a host handle has no such bound).
+ * rmx_learn_rmax_bind: a NULL rsum unbinds (Q-learning steps on the same tables again); a later rmx_learn_bind drops
+ * the binding; refused (RMX_E_STATE) while Q(lambda) lists are bound, as rmx_learn_lambda_bind is while a model is
+ * bound, and before rmx_learn_bind.  RMX_E_INVALID with a message, before any device work: threshold < 1, vi_delta not
+ * finite or <= 0, max_iter < 1, the learner's gamma >= 1, cap < 1 or above the full cap, a NULL or misaligned array
+ * (8, 4 and 4 bytes), a learner bound with use_rsh or without visits.
+ * rmx_learn_rmax_info: the solves made since the bind and the sweeps of the longest one (the converging sweep
+ * included); it synchronises a device handle.
+ * Not reproduced: noupdate_cnt and update's early-stop return value, QRMax_v2, UCBVI, OPSRL. */
+int rmx_learn_rmax_slots(const rmx_handle* h, int32_t* cap_full);
+int rmx_learn_rmax_bind(rmx_handle* h, int32_t threshold, double vi_delta, int vi_delta_rel, int32_t max_iter,
+                        int32_t cap, double* rsum, int32_t* succ_idx, int32_t* succ_cnt);
+int rmx_learn_rmax_info(rmx_handle* h, int64_t* solves, int64_t* max_sweeps);
 
 /* Synchronise and report kernel-side errors (e.g. RMX_E_ACTION), then clear them. */
 int rmx_check_errors(rmx_handle* h);

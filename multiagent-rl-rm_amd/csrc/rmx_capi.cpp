@@ -358,6 +358,7 @@ void rmx_destroy(rmx_handle* h) {
   (void)hipFree(h->d_rsc);
   (void)hipFree(h->seq.d_pk);
   (void)hipFree(h->learn.d_phi);
+  (void)hipFree(h->learn.d_rmax);
   delete h;
 }
 
@@ -615,6 +616,10 @@ int rmx_step_info(const rmx_handle* h, int64_t* out, int32_t n) {
 static const char kTraceFullMsg[] =
     "a Q(lambda) trace found its list full (rmx_learn_lambda_bind cap): the cell was updated, its trace not kept";
 
+static const char kModelFullMsg[] =
+    "an R-max successor found its list full (rmx_learn_rmax_bind cap): the observation was counted, its list entry "
+    "dropped";
+
 int rmx_check_errors(rmx_handle* h) {
   if (!h) return fail(RMX_E_INVALID, "handle is NULL");
   if (h->host) {
@@ -622,6 +627,7 @@ int rmx_check_errors(rmx_handle* h) {
     h->host->err = 0;
     if (err & 1u) return fail(RMX_E_ACTION, "an action outside [0,4] was stepped (treated as wait)");
     if (err & rmx::kErrTraceFull) return fail(RMX_E_TRACE, kTraceFullMsg);
+    if (err & rmx::kErrModelFull) return fail(RMX_E_MODEL, kModelFullMsg);
     return RMX_OK;
   }
   SYNC_END_OR_RETURN(h);
@@ -632,6 +638,7 @@ int rmx_check_errors(rmx_handle* h) {
   HIP_TRY(hipMemset(h->d_err, 0, sizeof(uint32_t)), "err clear");
   if (err & 1u) return fail(RMX_E_ACTION, "an action outside [0,4] was stepped (treated as wait)");
   if (err & rmx::kErrTraceFull) return fail(RMX_E_TRACE, kTraceFullMsg);
+  if (err & rmx::kErrModelFull) return fail(RMX_E_MODEL, kModelFullMsg);
   return RMX_OK;
 }
 

@@ -4,6 +4,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
+#include <string>
 #include <exception>
 #include <vector>
 
@@ -32,6 +34,13 @@ static int do_learn_step(rmx_handle* h, const int32_t* actions, rmx::LearnCall l
   p.seed = seed;
   p.t_global = t_global;
   p.autoreset = autoreset ? 1 : 0;
+  if (h->learn.rmax_on) {  // R-max: the step kernel, then with an update the solve kernel over the step's worklist
+    HIP_TRY(rmx::launch_learn_rmax(p, h->learn.params, lc, h->learn.rmax, h->learn.work, h->learn.rmax_grid, h->cfg.kind,
+                                   h->tables_bytes, as_stream(stream)),
+            "R-max learn step launch");
+    if (lc.update) h->learn.work.parity ^= 1;  // (the solve kernel has zeroed the other list's length)
+    return RMX_OK;
+  }
   // slip / random starts (a learner bound with RMX_LEARN_DYN_ENV): the kernel reads and writes the env generator and
   // episode columns rmx_bind required, and none of the fast path's caches (the reset cache, the next-episode shuffles)
   HIP_TRY(rmx::launch_learn_step(p, h->learn.params, lc, h->learn.lam_on ? &h->learn.lam : nullptr,
@@ -102,6 +111,7 @@ int rmx_learn_bind(rmx_handle* h, const rmx_learn_config* lc, double* q, double*
     h->host->learn = lp;
     h->host->learn_on = true;
     h->host->lam_on = false;  // a new learner: Q-learning until rmx_learn_lambda_bind
+    h->host->rmax_on = false; // or rmx_learn_rmax_bind
     h->host->eps = {};        // and the scalar epsilon until rmx_learn_eps_bind
     return RMX_OK;
   }
@@ -117,6 +127,7 @@ int rmx_learn_bind(rmx_handle* h, const rmx_learn_config* lc, double* q, double*
   h->learn.params = lp;
   h->learn.on = true;
   h->learn.lam_on = false;  // a new learner: Q-learning until rmx_learn_lambda_bind
+  h->learn.rmax_on = false; // or rmx_learn_rmax_bind
   h->learn.eps = {};        // and the scalar epsilon until rmx_learn_eps_bind
   return RMX_OK;
 }
@@ -182,6 +193,8 @@ int rmx_learn_lambda_bind(rmx_handle* h, double lambd, int32_t cap, int32_t* idx
       h->learn.lam_on = false;
     return RMX_OK;
   }
+  if (h->host ? h->host->rmax_on : h->learn.rmax_on)
+    return fail(RMX_E_STATE, "an R-max model is bound (rmx_learn_rmax_bind): unbind it before Q(lambda) lists");
   const rmx::LearnParams& lp = h->host ? h->host->learn : h->learn.params;
   if (lp.use_qrm || lp.use_rsh)
     return fail(RMX_E_INVALID, "Q(lambda) has no QRM and no shaping (the learner was bound with use_qrm / use_rsh)");
@@ -214,6 +227,117 @@ int rmx_learn_traces_clear(rmx_handle* h, const uint8_t* env_mask_dev, void* str
     return RMX_OK;
   }
   return lambda_clear(h, env_mask_dev, stream);
+}
+
+int rmx_learn_rmax_slots(const rmx_handle* h, int32_t* cap_full) {
+  if (!h || !cap_full) return fail(RMX_E_INVALID, "handle or cap_full is NULL");
+  int64_t s_max = 0;
+  const int rc = rmx_learn_states(h, &s_max);
+  if (rc) return rc;
+  if (s_max > INT32_MAX) return fail(RMX_E_INVALID, "S_max exceeds the int32 state indices of the successor lists");
+  *cap_full = rmx::kRMaxSlotsFull;
+  return RMX_OK;
+}
+
+int rmx_learn_rmax_bind(rmx_handle* h, int32_t threshold, double vi_delta, int vi_delta_rel, int32_t max_iter,
+                        int32_t cap, double* rsum, int32_t* succ_idx, int32_t* succ_cnt) {
+  if (!h) return fail(RMX_E_INVALID, "handle is NULL");
+  if (!(h->host ? h->host->learn_on : h->learn.on))
+    return fail(RMX_E_STATE, "no learner bound (rmx_learn_bind comes before rmx_learn_rmax_bind)");
+  if (!rsum) {  // back to Q-learning steps on the same tables
+    if (h->host)
+      h->host->rmax_on = false;
+    else
+      h->learn.rmax_on = false;
+    return RMX_OK;
+  }
+  if (h->host ? h->host->lam_on : h->learn.lam_on)
+    return fail(RMX_E_STATE, "Q(lambda) trace lists are bound (rmx_learn_lambda_bind): unbind them before an R-max model");
+  const rmx::LearnParams& lp = h->host ? h->host->learn : h->learn.params;
+  if (lp.use_rsh) return fail(RMX_E_INVALID, "R-max has no reward shaping (the learner was bound with use_rsh)");
+  if (!lp.visits) return fail(RMX_E_INVALID, "R-max needs the visits table (it serves as s_a_counts)");
+  if (!(lp.gamma < 1.0)) return fail(RMX_E_INVALID, "R-max needs gamma < 1 (value iteration on the learned MDP)");
+  if (threshold < 1) return fail(RMX_E_INVALID, "threshold (s_a_threshold) must be >= 1");
+  if (!std::isfinite(vi_delta) || vi_delta <= 0.0) return fail(RMX_E_INVALID, "vi_delta must be finite and > 0");
+  if (max_iter < 1) return fail(RMX_E_INVALID, "max_iter must be >= 1");
+  int32_t cap_full = 0;
+  const int rc = rmx_learn_rmax_slots(h, &cap_full);
+  if (rc) return rc;
+  if (cap < 1 || cap > cap_full) return fail(RMX_E_INVALID, "cap must be in [1, the full cap] (rmx_learn_rmax_slots)");
+  if (!succ_idx || !succ_cnt) return fail(RMX_E_INVALID, "succ_idx or succ_cnt is NULL");
+  if ((reinterpret_cast<uintptr_t>(rsum) & 7u) || (reinterpret_cast<uintptr_t>(succ_idx) & 3u) ||
+      (reinterpret_cast<uintptr_t>(succ_cnt) & 3u))
+    return fail(RMX_E_INVALID, "the model arrays must be aligned to their element types");
+  const int A = h->cfg.n_agents;
+  const int64_t N = h->cfg.n_envs, AN = (int64_t)A * N;
+  if (AN > INT32_MAX) return fail(RMX_E_INVALID, "A * N exceeds the int32 learner indices of the worklist");
+  const rmx::RMaxParams rp = {vi_delta, vi_delta_rel ? 1 : 0, max_iter, threshold, cap, rsum, succ_idx, succ_cnt};
+  if (h->host) {
+    try {
+      h->host->rmax_scratch.assign((size_t)lp.s_max * 5, 0.0);
+    } catch (const std::exception& e) {
+      return fail(RMX_E_INVALID, std::string("rmx_learn_rmax_bind: ") + e.what());
+    }
+    h->host->rmax = rp;
+    h->host->rmax_on = true;
+    h->host->rmax_solves = h->host->rmax_sweeps_max = 0;
+    return RMX_OK;
+  }
+  // the solve kernel keeps v of one learner double-buffered in LDS, 16 B per state: larger worlds are refused here
+  if (lp.s_max > rmx::kRMaxStatesMax)
+    return fail(RMX_E_INVALID, "S_max = " + std::to_string(lp.s_max) + " exceeds the " +
+                                   std::to_string((long long)rmx::kRMaxStatesMax) +
+                                   " states whose values the R-max solve kernel holds in LDS (16 B per state)");
+  SYNC_END_OR_RETURN(h);
+  HIP_TRY(hipSetDevice(h->device), "hipSetDevice");
+  // the hand-over between the two kernels, one allocation: counters and statistics | records | headers | worklist
+  const int32_t n_exp = 1 + h->cfg.n_qrm_max;
+  const size_t off_rec = 64, off_hdr = off_rec + sizeof(rmx::RMaxRec) * (size_t)AN * (size_t)n_exp,
+               off_list = off_hdr + 8 * (size_t)AN, bytes = off_list + 4 * (size_t)AN;
+  (void)hipFree(h->learn.d_rmax);
+  h->learn.d_rmax = nullptr;
+  HIP_TRY(hipMalloc(&h->learn.d_rmax, bytes), "R-max worklist alloc");
+  HIP_TRY(hipMemset(h->learn.d_rmax, 0, bytes), "R-max worklist clear");
+  rmx::RMaxWork wk{};
+  wk.count = reinterpret_cast<uint32_t*>(h->learn.d_rmax);
+  wk.stats = reinterpret_cast<unsigned long long*>(h->learn.d_rmax + 16);
+  wk.recs = reinterpret_cast<rmx::RMaxRec*>(h->learn.d_rmax + off_rec);
+  wk.hdr = reinterpret_cast<int32_t*>(h->learn.d_rmax + off_hdr);
+  wk.list = reinterpret_cast<int32_t*>(h->learn.d_rmax + off_list);
+  wk.n_exp = n_exp;
+  wk.parity = 0;
+  for (int a = 0; a < A; ++a) wk.S[a] = h->cfg.width * h->cfg.height * h->enc_nq[a];
+  wk.N = N;
+  wk.n_learners = AN;
+  wk.err = h->d_err;
+  h->learn.work = wk;
+  h->learn.rmax = rp;
+  h->learn.rmax_grid = rmx::kRMaxGrid;
+  if (const char* g = std::getenv("RMX_RMAX_GRID")) {  // tests: a grid smaller than a step's worklist
+    const long v = std::strtol(g, nullptr, 10);
+    if (v >= 1 && v <= 65536) h->learn.rmax_grid = (int)v;
+  }
+  h->learn.rmax_on = true;
+  return RMX_OK;
+}
+
+int rmx_learn_rmax_info(rmx_handle* h, int64_t* solves, int64_t* max_sweeps) {
+  if (!h || !solves || !max_sweeps) return fail(RMX_E_INVALID, "handle, solves or max_sweeps is NULL");
+  if (!(h->host ? h->host->rmax_on : h->learn.rmax_on))
+    return fail(RMX_E_STATE, "no R-max model bound (rmx_learn_rmax_bind)");
+  if (h->host) {
+    *solves = h->host->rmax_solves;
+    *max_sweeps = h->host->rmax_sweeps_max;
+    return RMX_OK;
+  }
+  SYNC_END_OR_RETURN(h);
+  HIP_TRY(hipSetDevice(h->device), "hipSetDevice");
+  HIP_TRY(hipDeviceSynchronize(), "sync");
+  unsigned long long st[2] = {0, 0};
+  HIP_TRY(hipMemcpy(st, h->learn.work.stats, sizeof(st), hipMemcpyDeviceToHost), "R-max statistics copy");
+  *solves = (int64_t)st[0];
+  *max_sweeps = (int64_t)st[1];
+  return RMX_OK;
 }
 
 int rmx_learn_eps_bind(rmx_handle* h, double* eps, double eps_end, double eps_decay) {
@@ -279,6 +403,9 @@ int rmx_learn_run(rmx_handle* h, int32_t T, double epsilon, int flags, uint64_t 
   if (flags & ~(RMX_LEARN_UPDATE | RMX_LEARN_BEST | RMX_LEARN_NUMPY)) return fail(RMX_E_INVALID, "unknown learn step flags");
   if (!h->bound) return fail(RMX_E_STATE, "buffers not bound (rmx_bind)");
   if (!(h->host ? h->host->learn_on : h->learn.on)) return fail(RMX_E_STATE, "no learner bound (rmx_learn_bind)");
+  if (h->host ? h->host->rmax_on : h->learn.rmax_on)
+    return fail(RMX_E_STATE, "rmx_learn_run does not serve R-max learners (one thread per env cannot run a "
+                             "workgroup-wide solve): loop rmx_learn_step_policy");
   rmx::LearnCall lc{};
   lc.epsilon = epsilon;
   lc.policy = (flags & RMX_LEARN_NUMPY) ? rmx::kLearnNumpy : rmx::kLearnHash;

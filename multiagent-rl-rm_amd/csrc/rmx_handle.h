@@ -138,6 +138,13 @@ struct rmx_handle {
     bool lam_on = false;
     // rmx_learn_eps_bind: the per-learner epsilon schedule over the caller's column [A][N] (eps.col == NULL: none)
     rmx::EpsParams eps{};
+    // rmx_learn_rmax_bind: the learners are R-max ones over the caller's model arrays (rmax_on); the engine's own
+    // hand-over between the step kernel and the solve kernel (one allocation, d_rmax), the solve kernel's grid
+    rmx::RMaxParams rmax{};
+    bool rmax_on = false;
+    rmx::RMaxWork work{};
+    unsigned char* d_rmax = nullptr;
+    int rmax_grid = rmx::kRMaxGrid;
   } learn;
 };
 

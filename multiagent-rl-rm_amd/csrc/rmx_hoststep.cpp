@@ -200,6 +200,25 @@ void HostEngine::traces_clear(const uint8_t* mask) {
   }
 }
 
+uint32_t HostEngine::rmax_agent(const LearnTables& T, const LearnStep& st, int a, int64_t e, int k) {
+  const int64_t S = mdp_states(a);
+  const RMaxLearner L = rmax_learner(learn, rmax, (int64_t)a * cfg.n_envs + e);
+  uint32_t bad = 0;
+  const int n = rmax_n_exp(learn, T);
+  for (int j = 0; j < n; ++j) {
+    LearnExp x;
+    if (!rmax_experience(learn, T, st, j, S, x)) continue;
+    const int res = rmax_update_q(rmax, L, x, k);
+    if (res & kRMaxFull) bad |= (uint32_t)kErrModelFull;
+    if (res & kRMaxCross) {  // solved before the next experience of the same step
+      const int sweeps = rmax_solve(rmax, learn.gamma, L, S, rmax_scratch.data(), rmax_scratch.data() + learn.s_max);
+      ++rmax_solves;
+      rmax_sweeps_max = std::max<int64_t>(rmax_sweeps_max, sweeps);
+    }
+  }
+  return bad;
+}
+
 void HostEngine::eps_decay(const uint8_t* mask) {
   const int64_t N = cfg.n_envs;
   for (int64_t e = 0; e < N; ++e) {
@@ -247,7 +266,7 @@ uint32_t HostEngine::step_kind(const int32_t* actions, int autoreset, bool hashe
       reset_regs(s, t, p);
       // a learn step's reset is learn_done_episode for every agent's learner: a policy step decays where it reads the
       // learner's epsilon below, a step on the caller's actions here (as the kernel)
-      if (lc && !lc->policy && eps.col) learn_eps_reset(eps, A, N, e);
+      if (lc && !lc->policy && eps.col && !rmax_on) learn_eps_reset(eps, A, N, e);
       if (lc && lam_on)  // a learn step's reset clears the traces of every agent's learner
         for (int a = 0; a < A; ++a) lam.cnt[(int64_t)a * N + e] = 0;
       if (rng_on) {  // env.rng = default_rng(seed of the next episode)
@@ -267,6 +286,27 @@ uint32_t HostEngine::step_kind(const int32_t* actions, int autoreset, bool hashe
                                 ? learn.q + (((int64_t)a * N + e) * learn.s_max + st) * 4
                                 : none;
         // the learner's own epsilon with a schedule bound (decayed under RMX_LEARN_BEST too), else the call's
+        if (rmax_on) {  // R-max has no epsilon: a flat row draws, any other takes its first maximum
+          if (lc->policy == kLearnNumpy && !lc->best) {
+            if (rmax_row_flat(row[0], row[1], row[2], row[3])) {  // (no draw otherwise: the column is not touched)
+              const int64_t plane = (int64_t)A * N;
+              uint64_t* w = lc->rng + (int64_t)a * N + e;
+              const uint64_t w4 = w[4 * plane];
+              LearnRng r = {{w[0], w[plane], w[2 * plane], w[3 * plane]}, (uint32_t)(w4 >> 32), (uint32_t)w4};
+              act[a] = rmax_policy_numpy(r, row[0], row[1], row[2], row[3]);
+              w[0] = r.hi;
+              w[plane] = r.lo;
+              if (learn_rng_word4(r) != w4) w[4 * plane] = learn_rng_word4(r);
+            } else {
+              act[a] = rmax_argmax(row[0], row[1], row[2], row[3]);
+            }
+          } else {
+            act[a] = rmax_policy(seed, t_global, cfg.n_envs_global, cfg.env_offset + e, A, a, lc->best, row[0], row[1],
+                                 row[2], row[3]);
+          }
+          if (lc->actions_out) lc->actions_out[(int64_t)a * N + e] = act[a];
+          continue;
+        }
         const double epsilon = eps.col ? learn_eps_step(eps, a, N, e, was_reset) : lc->epsilon;
         if (lc->policy == kLearnNumpy && !lc->best) {  // the learner's own numpy generator (RMX_LEARN_NUMPY)
           const int64_t plane = (int64_t)A * N;
@@ -329,7 +369,9 @@ uint32_t HostEngine::step_kind(const int32_t* actions, int autoreset, bool hashe
                               o[a].env_term,  o[a].term, o[a].trunc, o[a].renv};
         const int64_t base = ((int64_t)a * N + e) * learn.s_max * 4;
         double* va = learn.visits ? learn.visits + base : nullptr;
-        if (lam_on)
+        if (rmax_on)
+          bad |= rmax_agent(T, st, a, e, act[a]);
+        else if (lam_on)
           bad |= learn_lambda_agent(learn, lam, T, st, learn.q + base, va, act[a], mdp_states(a), a, N, e)
                      ? (uint32_t)kErrTraceFull
                      : 0u;

@@ -15,6 +15,7 @@
 #include "../../include/rmx.h"
 #include "rmx_host.h"
 #include "rmx_learn.h"
+#include "rmx_rmax.h"
 #include "rmx_rules.h"
 
 namespace rmx {
@@ -58,7 +59,9 @@ struct HostEngine {
   int32_t* enc = nullptr;
   uint64_t base_seed = 123;
   double stats[RMX_NSTATS]{};
-  uint32_t err = 0;       // bit 0: an invalid action was stepped; kErrTraceFull: a full trace list (rmx_check_errors)
+  // bit 0: an invalid action was stepped; kErrTraceFull: a full trace list; kErrModelFull: a full R-max successor
+  // list (rmx_check_errors)
+  uint32_t err = 0;
   bool pending = false;   // rmx_step_sync_begin ran a step whose outputs rmx_sync_wait has not returned
   uint32_t pending_bad = 0;
   bool last_reset = false;  // the synchronous call before the copy was a reset (no step outputs)
@@ -73,6 +76,15 @@ struct HostEngine {
   // rmx_learn_eps_bind: the per-learner epsilon schedule over the caller's column [A][N] (col == NULL: none); only
   // learn steps and eps_decay touch it
   EpsParams eps{};
+  // rmx_learn_rmax_bind: R-max learners over the caller's model arrays (host pointers); the solve's scratch (v of
+  // S_max, new of 4 * S_max doubles).  A learn step's update is then rmax_agent, its policy rmax_policy*, and the
+  // epsilon column is left alone.
+  RMaxParams rmax{};
+  bool rmax_on = false;
+  std::vector<double> rmax_scratch;
+  int64_t rmax_solves = 0, rmax_sweeps_max = 0;  // solves so far, the longest one's sweeps (tests)
+  // every experience of one agent-step in order, each crossing solved at once; kErrModelFull or 0
+  uint32_t rmax_agent(const LearnTables& T, const LearnStep& st, int a, int64_t e, int k);
   // learn_done_episode of every agent's learner of the masked envs (NULL: every env); a column must be bound
   void eps_decay(const uint8_t* mask);
   // cnt[a][e] = 0 for the masked envs (NULL: every env); nothing without Q(lambda) bound

@@ -9,6 +9,7 @@
 #include "../../include/rmx.h"
 #include "rmx_layout.h"
 #include "rmx_learn.h"
+#include "rmx_rmax.h"
 #include "rmx_rules.h"
 
 namespace rmx {
@@ -388,6 +389,10 @@ hipError_t launch_learn_step_eps(const KParams& p, const LearnParams& lp, const 
                                  const EpsParams* eps, int kind, size_t lds, hipStream_t st);
 hipError_t launch_learn_run_eps(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
                                 const EpsParams* eps, int32_t T, int kind, size_t lds, hipStream_t st);
+// The R-max learn step (rmx_learn_rmax.hip): the step kernel with every learner's model update up to its first
+// crossing, then (lc.update) the solve kernel over the step's worklist, `grid` workgroups
+hipError_t launch_learn_rmax(const KParams& p, const LearnParams& lp, const LearnCall& lc, const RMaxParams& rp,
+                             const RMaxWork& wk, int grid, int kind, size_t lds, hipStream_t st);
 // cnt[a][e] = 0 for every env of the device mask (NULL: every env)
 hipError_t launch_traces_clear(int32_t* cnt, const uint8_t* mask, int A, int64_t N, hipStream_t st);
 // rmx_learn_eps_decay: learn_done_episode of every agent's learner of every env of the device mask (NULL: every env)

@@ -15,6 +15,7 @@ LIB_NAME = "librmx.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
 RMX_OK, RMX_E_INVALID, RMX_E_HIP, RMX_E_ACTION, RMX_E_STATE, RMX_E_TRACE = 0, -1, -2, -3, -4, -5
+RMX_E_MODEL = -6
 F_ACTIVE, F_FAIL, F_TERM, F_TRUNC, F_ENV_TERM, F_RM_TERM, F_ENV_DONE = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
 F_STEPS_SHIFT = 16
 NSTATS = 4
@@ -32,6 +33,7 @@ EXPORTS = (
     "rmx_learn_step_policy", "rmx_learn_rng_bind", "rmx_learn_rng_seed", "rmx_learn_lambda_slots",
     "rmx_learn_lambda_bind",
     "rmx_learn_traces_clear", "rmx_learn_run", "rmx_learn_eps_bind", "rmx_learn_eps_decay",
+    "rmx_learn_rmax_slots", "rmx_learn_rmax_bind", "rmx_learn_rmax_info",
 )
 LEARN_UPDATE, LEARN_BEST, LEARN_NUMPY = 1, 2, 4  # RMX_LEARN_*
 LEARN_DYN_FIXED, LEARN_DYN_ENV = 0, 1  # rmx_learn_config.dynamics
@@ -62,7 +64,7 @@ HASHED_SOURCES = ("rmx_kernels.hip", "rmx_fast.hip", "rmx_fast_step.inc", "rmx_s
                   "rmx_comd.cpp", "rmx_build_info.cpp", "rmx_internal.h", "rmx_layout.h", "rmx_host.h", "rmx_device.h",
                   "rmx_generic.h", "rmx_comd.h", "rmx_hoststep.cpp", "rmx_hoststep.h", "rmx_learn.hip", "rmx_learn_run.hip", "rmx_learn.h",
                   "rmx_rules.h", "../../include/rmx.h",
-                  "Makefile", "rmx_learn_eps.hip", "rmx_learn_run_eps.hip")
+                  "Makefile", "rmx_learn_eps.hip", "rmx_learn_run_eps.hip", "rmx_rmax.h", "rmx_learn_rmax.hip")
 
 
 def source_hash(csrc: str = CSRC) -> str:
@@ -247,6 +249,9 @@ def load_library(path: str = None, check_source: bool = True):
         "rmx_learn_traces_clear": (C.c_int, [vp, vp, vp]),
         "rmx_learn_eps_bind": (C.c_int, [vp, vp, C.c_double, C.c_double]),
         "rmx_learn_eps_decay": (C.c_int, [vp, vp, vp]),
+        "rmx_learn_rmax_slots": (C.c_int, [vp, C.POINTER(C.c_int32)]),
+        "rmx_learn_rmax_bind": (C.c_int, [vp, i32, C.c_double, C.c_int, i32, i32, vp, vp, vp]),
+        "rmx_learn_rmax_info": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -388,3 +388,122 @@ class VecQLambda(VecQLearning):
         """Empty the lists of the masked envs ([N] bool / uint8; None: every env)."""
         _capi.check(self.lib.rmx_learn_traces_clear(self.env._h, self._mask_ptr(mask), self._stream()),
                     "rmx_learn_traces_clear")
+
+
+class VecRMax(VecQLearning):
+    """One R-max learner per (env, agent): the reference's ``RMax`` (learning_algorithms/rmax.py) as
+    ``AgentRL.update_policy`` drives it, which is what the OfficeWorld runner's ``--algorithm RMAX`` / ``RMAXRM``
+    (``use_qrm``) build (include/rmx.h, "R-max learners").  Every learner keeps its own model: ``counts`` (the bound
+    ``visits`` table, the reference's ``s_a_counts``), ``rsum`` (``rewards``) ``[A, N, S_max, 4]`` float64, and the
+    non-zero entries of the reference's dense ``transitions`` as lists ``succ_idx`` / ``succ_cnt``
+    ``[A, N, S_max, 4, cap]`` int32 in first-seen order; ``q`` starts at ``max_reward / (1 - gamma)``.  The observation
+    that brings a pair to ``s_a_threshold`` solves the learner's MDP by value iteration at once (``vi_delta``,
+    ``vi_delta_rel``, at most ``max_iter`` sweeps).  On a GPU env a learn step is the step kernel plus a solve kernel
+    that walks the learners with a solve pending (csrc/rmx_learn_rmax.hip); a host env runs the same functions in order.
+
+    ``step``, ``act_step``, ``run``, ``greedy`` and the generator accessors are ``VecQLearning``'s.  There is no
+    epsilon: ``act_step`` / ``run`` take none (passing one raises); a flat row draws one of the four actions, any
+    other row takes its first maximum.  ``succ_cap`` (default: ``rmx_learn_rmax_slots``, which cannot overflow) is
+    cap; a successor that finds its list full is dropped from the list (still counted) and ``env.check_errors()``
+    raises ``RuntimeError``.  No reset touches the model.  Not reproduced: ``noupdate_cnt`` and the early-stop return
+    value of ``update``, ``QRMax_v2``, ``UCBVI``, ``OPSRL``."""
+
+    def __init__(self, env, gamma, s_a_threshold=100, max_reward=1.0, vi_delta=1e-4, vi_delta_rel=False, use_qrm=False,
+                 trunc_is_terminal=None, policy_seeds=None, succ_cap=None, max_iter=10000):
+        if not float(gamma) < 1.0:
+            raise ValueError("R-max needs gamma < 1")
+        super().__init__(env, gamma, learning_rate=1.0, qtable_init=float(max_reward) / (1.0 - float(gamma)),
+                         use_qrm=use_qrm, use_rsh=False, trunc_is_terminal=trunc_is_terminal, policy_seeds=policy_seeds)
+        self.learning_rate = None  # (R-max has none; the Q-learning steps after unbind() run at rate 1)
+        full = C.c_int32()
+        _capi.check(self.lib.rmx_learn_rmax_slots(env._h, C.byref(full)), "rmx_learn_rmax_slots")
+        self.succ_full = int(full.value)
+        self.succ_cap = self.succ_full if succ_cap is None else int(succ_cap)
+        self.s_a_threshold, self.max_reward = int(s_a_threshold), float(max_reward)
+        self.vi_delta, self.vi_delta_rel, self.max_iter = float(vi_delta), bool(vi_delta_rel), int(max_iter)
+        self.counts = self.visits
+        cap = max(self.succ_cap, 1)  # (a refused cap is refused by the bind below, not by the allocation)
+        shape = (env.A, env.N, self.S_max, 4)
+        if self.host:
+            self.rsum = np.zeros(shape, np.float64)
+            self.succ_idx = np.zeros(shape + (cap,), np.int32)
+            self.succ_cnt = np.zeros(shape + (cap,), np.int32)
+        else:
+            t = env.torch
+            self.rsum = t.zeros(shape, dtype=t.float64, device=env.device)
+            self.succ_idx = t.zeros(shape + (cap,), dtype=t.int32, device=env.device)
+            self.succ_cnt = t.zeros(shape + (cap,), dtype=t.int32, device=env.device)
+        self.bind_model(self.rsum, self.succ_idx, self.succ_cnt, self.succ_cap)
+
+    def _ptr(self, x):
+        return x.ctypes.data if self.host else x.data_ptr()
+
+    def bind_model(self, rsum, succ_idx, succ_cnt, cap):
+        """rmx_learn_rmax_bind with the caller's own arrays (numpy on a host env, tensors or views on a GPU env)."""
+        _capi.check(self.lib.rmx_learn_rmax_bind(self.env._h, self.s_a_threshold, self.vi_delta,
+                                                 int(self.vi_delta_rel), self.max_iter, int(cap), self._ptr(rsum),
+                                                 self._ptr(succ_idx), self._ptr(succ_cnt)), "rmx_learn_rmax_bind")
+        self.rsum, self.succ_idx, self.succ_cnt, self.succ_cap = rsum, succ_idx, succ_cnt, int(cap)
+
+    def unbind(self):
+        """Back to plain Q-learning steps on the same tables (``bind_model`` binds the model again)."""
+        _capi.check(self.lib.rmx_learn_rmax_bind(self.env._h, 0, 0.0, 0, 0, 0, None, None, None), "rmx_learn_rmax_bind")
+
+    def _epsilon_arg(self, epsilon):
+        if epsilon is not None:
+            raise ValueError("R-max has no epsilon: epsilon must be None")
+        return 0.0
+
+    def run(self, T, epsilon=None, seed=None, t_global=None, best=False, learn=True, reference_stream=False,
+            actions_out=None):
+        """``T`` consecutive auto-resetting ``act_step``s (global steps ``t_global .. t_global + T - 1``), with the
+        result contract of ``VecQLearning.run``: the tables, the model, every column and the generators end as the T
+        single steps leave them, because they ARE the T single steps: rmx_learn_run does not serve R-max (one thread
+        per env cannot run a workgroup-wide solve), so this loops ``act_step`` in Python, one call and at most two
+        launches per step.  ``actions_out``: a contiguous int32 ``[T, A, N]`` tensor (an array on a host env)."""
+        env = self.env
+        self._epsilon_arg(epsilon)
+        T = int(T)
+        if T < 1:
+            raise ValueError("T must be >= 1")
+        AN = env.A * env.N
+        if actions_out is not None:
+            if self.host:
+                flat = env._out(actions_out, np.int32, T * AN, "actions_out").reshape(-1)
+            else:
+                t = env.torch
+                if actions_out.dtype is not t.int32 or actions_out.get_device() != env.device.index or \
+                        not actions_out.is_contiguous() or actions_out.numel() < T * AN:
+                    raise ValueError("actions_out must be a contiguous int32 [T, A, N] tensor on the engine's device")
+                flat = actions_out.view(-1)
+        for k in range(T):
+            self.act_step(None, seed, None if t_global is None else int(t_global) + k, best=best, learn=learn,
+                          actions_out=None if actions_out is None else flat[k * AN:(k + 1) * AN],
+                          reference_stream=reference_stream)
+        return actions_out
+
+    def _np(self, x):
+        if self.host:
+            return x
+        self.env.sync_end()
+        return x.cpu().numpy()
+
+    def known(self):
+        """``counts >= s_a_threshold``: [A, N, S_max, 4] bool (numpy), the pairs value iteration writes."""
+        return self._np(self.counts) >= self.s_a_threshold
+
+    def transitions(self):
+        """The reference's dense ``transitions`` rebuilt from the lists: [A, N, S_max, 4, S_max] float64 (numpy)."""
+        idx, cnt = self._np(self.succ_idx), self._np(self.succ_cnt)
+        A, N, S, _, cap = cnt.shape
+        out = np.zeros((A, N, S, 4, S), np.float64)
+        a, e, s, k, j = np.nonzero(cnt)
+        out[a, e, s, k, idx[a, e, s, k, j]] = cnt[a, e, s, k, j]
+        return out
+
+    def solve_info(self):
+        """``(solves, max_sweeps)``: the solves made since the model was bound, and the sweeps of the longest one
+        (the converging sweep included).  Synchronises a GPU env."""
+        n, m = C.c_int64(), C.c_int64()
+        _capi.check(self.lib.rmx_learn_rmax_info(self.env._h, C.byref(n), C.byref(m)), "rmx_learn_rmax_info")
+        return int(n.value), int(m.value)
