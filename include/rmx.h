@@ -663,6 +663,82 @@ int rmx_learn_rmax_bind(rmx_handle* h, int32_t threshold, double vi_delta, int v
                         int32_t cap, double* rsum, int32_t* succ_idx, int32_t* succ_cnt);
 int rmx_learn_rmax_info(rmx_handle* h, int64_t* solves, int64_t* max_sweeps);
 
+/* ---- QR-max learners: a factored environment / RM model per learner, solved by value iteration -----------------
+ * QRMax_v2 (learning_algorithms/qrmax_v2.py) behind AgentRL.update_policy, as the OfficeWorld runner builds it for
+ * --algorithm QRMAX / QRMAXRM (create_qrmax, office_main.py:720-746): one learner per (agent a, env e).
+ * rmx_learn_bind comes first: q is filled by the caller, per agent, with max_reward * enc_nq[a] / (1 - gamma) (R_max =
+ * max_reward * nQ, qrmax_v2.py:38, 49); the visits table serves as nTSQA and is required; use_rsh is refused;
+ * learning_rate is unused.  rmx_learn_qrmax_bind then turns the handle's learners into QR-max ones; rmx_learn_step and
+ * rmx_learn_step_policy run the QR-max learn step (a device handle: at most two launches on the caller's stream,
+ * rmx_learn_qrmax.hip; no device synchronisation).
+ * Indices: s = y*W + x is the position (info["s"]), q the RM state index, P = W*H, nQ = enc_nq[a].  Q[s, q, a] is
+ * q[(s*nQ + q)*4 + a] of the bound table.
+ * Caller-owned arrays beside q and visits, learner-major, zeroed by the caller:
+ *   known_tsqa uint8 [A][N][S_max][4]                      knownTSQA, the one known flag that needs stored state
+ *   n_tsa, n_rsa int32, sum_rsa float64 [A][N][P][4]       nTSA, nRSA, sumRSA
+ *   succ_idx, succ_cnt int32 [A][N][P][4][cap]             nTSAS_dict[(s, a)] in first-seen order with nTSAS; a slot
+ *                                                          with succ_cnt == 0 is empty
+ *   n_tqs, tq_next, n_rqs int32, sum_rqs float64 [A][N][S_max]   nTQS, the successor q' of (q, s'), nRQS, sumRQS,
+ *                                                          all indexed by the encoded (s', q) = s'*nQ + q
+ *   final uint8 [A][N][S_max]                              final_states as a mask over s*nQ + q
+ * With thresholds >= 1 every known flag but knownTSQA equals count >= threshold between two experiences, so the
+ * others are not stored: knownTSA = n_tsa >= nsamples_te, knownRSA = n_rsa >= nsamples_re, knownTQS = n_tqs >=
+ * nsamples_tq, knownRQS = n_rqs >= nsamples_rq.
+ * One update (qrmax_v2.py:414-506).  Experiences of one agent-step: the real one first (s, q, a, s1, q1, re = Renv, rq =
+ * RQ = (double)reward_modifier*(double)rm_reward, the done rule of trunc_is_terminal), then with use_qrm every
+ * counterfactual in get_all_states()[:-1] order (the same a and re, rq the raw RM reward, done = env_term or rm_done),
+ * the RM state actually held included once more.  An action without a table column, or an experience with a
+ * position or RM index outside the agent's own, is dropped.  Each experience, in this order:
+ *   1. update_RSQA_RSA: done: final[s1*nQ + q1] = 1.  knownTSQA[s,q,a] == 0: visits[s,q,a] += 1.  knownTSA[s,a] == 0:
+ *      the count of s1 in the list of (s, a) += 1 (appended with count 1 if new), n_tsa[s,a] += 1.  knownRSA[s,a] == 0:
+ *      n_rsa[s,a] += 1, sum_rsa[s,a] += re (one float64 add).
+ *   2. update_TQS_RQS: knownTQS[q,s1] == 0: n_tqs += 1, tq_next = q1.  knownRQS[q,s1] == 0: n_rqs += 1, sum_rqs += rq.
+ *   3. check_known, in the reference's order: knownTSQA[s,q,a] is set if visits[s,q,a] >= nsamples_te, or by the
+ *      shortcut: knownTSA[s,a] ALREADY set when this experience arrived and knownTQS[q,ss1], likewise as it stood
+ *      when this experience arrived for ss1 == s1, for every listed successor ss1 of (s, a).  Then knownTSA,
+ *      knownTQS[q,s1], knownRSA, knownRQS[q,s1] by their counts.
+ * If any experience of the agent-step made something newly known, ONE solve_VI runs behind the last experience.
+ * solve_VI (qrmax_v2.py:265-338): q[s,q,:] = 0 for every final (s, q) (here, not when the state was marked: the
+ * policy sees the old row until the next solve).  delta = 1.0; while delta > vi_delta and fewer than max_iter sweeps
+ * (the reference: 10000): a Jacobi sweep over every (s, q, a) with knownTSA && knownRSA && knownTSQA and (s, q) not
+ * final:  rsa = sum_rsa/n_rsa;  for each listed s1 of (s, a) in list order with n_tqs[q,s1] > 0, q1 its successor:
+ * tr = (n/n) * (cnt/n_tsa), the first factor 1.0 exactly; rqs = n_rqs > 0 ? sum_rqs/n_rqs : 0; qq1 += tr*(rsa + rqs);
+ * qq2 += tr*max_a Q_old[s1,q1];  a successor whose (q, s1) was never observed contributes nothing;  Qnew = qq1 +
+ * gamma*qq2;  cdelta = |Qnew - Qold|, under vi_delta_rel divided by m = |max(Qnew, Qold)| where m > 0;  delta is the
+ * largest cdelta of the sweep (a NaN never raises it);  Q = Qnew after every sweep, the last one included.  Every
+ * step is one IEEE float64 operation, never fused; the sums start from +0.0 in list order.  solve_VI is a scalar
+ * loop over the learner's own lists, so every table equals the reference's bit for bit, on slip worlds too.
+ * Policy (qrmax_v2.py:216-232): there is no epsilon (rmx_learn_step_policy validates its scalar and ignores it; a
+ * bound epsilon column is left alone).  Under RMX_LEARN_NUMPY every call first shuffles the list of the four actions
+ * on the learner's own generator (numpy's untyped Fisher-Yates: for i = 3, 2, 1 swap with random_interval(i) on
+ * buffered 32-bit draws), under RMX_LEARN_BEST too; a flat row, unless RMX_LEARN_BEST, takes the shuffled list at
+ * integers(0, 4); any other row its first maximum.  Under the engine's hashed policy a flat row takes h0 >> 62 and
+ * nothing is drawn.  A state outside the agent's rows reads as four zeros, which is the flat case.
+ * Capacity: rmx_learn_qrmax_slots() = 5 can never overflow: the position after an agent-step is the agent's own cell
+ * or one of its four neighbours (the R-max derivation above, with positions in place of encoded states).  A caller
+ * may bind fewer.  A successor that finds its list full is still counted in n_tsa, its entry is dropped, and the
+ * error word gets the bit rmx_check_errors reports as RMX_E_MODEL.  Nothing is written at or past slot cap.
+ * None of the arrays is part of rmx_get_state, and no reset touches them.  rmx_learn_run on a handle with QR-max
+ * bound: RMX_E_STATE; a caller loops rmx_learn_step_policy.  A device handle keeps the values of the learner being
+ * solved in LDS, 16 B per state: S_max above 4064 is refused at bind (a host handle has no such bound).
+ * rmx_learn_qrmax_bind: a NULL known_tsqa unbinds (Q-learning steps on the same tables again); a later rmx_learn_bind
+ * drops the binding; refused (RMX_E_STATE) while Q(lambda) lists or an R-max model are bound, as those binds are while
+ * a QR-max model is bound, and before rmx_learn_bind.  RMX_E_INVALID with a message, before any device work: a
+ * threshold < 1, vi_delta not finite or <= 0, max_iter < 1, the learner's gamma >= 1, cap < 1 or above the full cap, a
+ * NULL or misaligned array, a learner bound with use_rsh or without visits.
+ * rmx_learn_qrmax_info: the solves made since the bind, the sweeps of the longest one and the sweeps of all of them; it
+ * synchronises a device handle.
+ * Not reproduced: noupdate_cnt and update's early-stop return value; reset_VI; tosolve_VI / learn_done_episode (never
+ * armed); save_environment / load_environment (the model arrays are the caller's: copy them); the bookkeeping no
+ * computation reads (nTSQAS, nTSQA_dict, entrySQ_dict, nRSQA, nRSQASQ, sumR, pTSAS); UCBVI, OPSRL. */
+int rmx_learn_qrmax_slots(const rmx_handle* h, int32_t* cap_full);
+int rmx_learn_qrmax_bind(rmx_handle* h, int32_t nsamples_te, int32_t nsamples_re, int32_t nsamples_tq,
+                         int32_t nsamples_rq, double vi_delta, int vi_delta_rel, int32_t max_iter, int32_t cap,
+                         uint8_t* known_tsqa, int32_t* n_tsa, int32_t* n_rsa, double* sum_rsa, int32_t* succ_idx,
+                         int32_t* succ_cnt, int32_t* n_tqs, int32_t* tq_next, int32_t* n_rqs, double* sum_rqs,
+                         uint8_t* final);
+int rmx_learn_qrmax_info(rmx_handle* h, int64_t* solves, int64_t* max_sweeps, int64_t* total_sweeps);
+
 /* Synchronise and report kernel-side errors (e.g. RMX_E_ACTION), then clear them. */
 int rmx_check_errors(rmx_handle* h);
 

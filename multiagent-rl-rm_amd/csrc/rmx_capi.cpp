@@ -359,6 +359,7 @@ void rmx_destroy(rmx_handle* h) {
   (void)hipFree(h->seq.d_pk);
   (void)hipFree(h->learn.d_phi);
   (void)hipFree(h->learn.d_rmax);
+  (void)hipFree(h->learn.d_qrmax);
   delete h;
 }
 

@@ -34,6 +34,13 @@ static int do_learn_step(rmx_handle* h, const int32_t* actions, rmx::LearnCall l
   p.seed = seed;
   p.t_global = t_global;
   p.autoreset = autoreset ? 1 : 0;
+  if (h->learn.qrmax_on) {  // QR-max: likewise, over the learners with something newly known
+    HIP_TRY(rmx::launch_learn_qrmax(p, h->learn.params, lc, h->learn.qrmax, h->learn.qwork, h->learn.qrmax_grid,
+                                    h->cfg.kind, h->tables_bytes, as_stream(stream)),
+            "QR-max learn step launch");
+    if (lc.update) h->learn.qwork.parity ^= 1;  // (the solve kernel has zeroed the other list's length)
+    return RMX_OK;
+  }
   if (h->learn.rmax_on) {  // R-max: the step kernel, then with an update the solve kernel over the step's worklist
     HIP_TRY(rmx::launch_learn_rmax(p, h->learn.params, lc, h->learn.rmax, h->learn.work, h->learn.rmax_grid, h->cfg.kind,
                                    h->tables_bytes, as_stream(stream)),
@@ -112,6 +119,7 @@ int rmx_learn_bind(rmx_handle* h, const rmx_learn_config* lc, double* q, double*
     h->host->learn_on = true;
     h->host->lam_on = false;  // a new learner: Q-learning until rmx_learn_lambda_bind
     h->host->rmax_on = false; // or rmx_learn_rmax_bind
+    h->host->qrmax_on = false;  // or rmx_learn_qrmax_bind
     h->host->eps = {};        // and the scalar epsilon until rmx_learn_eps_bind
     return RMX_OK;
   }
@@ -128,6 +136,7 @@ int rmx_learn_bind(rmx_handle* h, const rmx_learn_config* lc, double* q, double*
   h->learn.on = true;
   h->learn.lam_on = false;  // a new learner: Q-learning until rmx_learn_lambda_bind
   h->learn.rmax_on = false; // or rmx_learn_rmax_bind
+  h->learn.qrmax_on = false;  // or rmx_learn_qrmax_bind
   h->learn.eps = {};        // and the scalar epsilon until rmx_learn_eps_bind
   return RMX_OK;
 }
@@ -195,6 +204,8 @@ int rmx_learn_lambda_bind(rmx_handle* h, double lambd, int32_t cap, int32_t* idx
   }
   if (h->host ? h->host->rmax_on : h->learn.rmax_on)
     return fail(RMX_E_STATE, "an R-max model is bound (rmx_learn_rmax_bind): unbind it before Q(lambda) lists");
+  if (h->host ? h->host->qrmax_on : h->learn.qrmax_on)
+    return fail(RMX_E_STATE, "a QR-max model is bound (rmx_learn_qrmax_bind): unbind it before Q(lambda) lists");
   const rmx::LearnParams& lp = h->host ? h->host->learn : h->learn.params;
   if (lp.use_qrm || lp.use_rsh)
     return fail(RMX_E_INVALID, "Q(lambda) has no QRM and no shaping (the learner was bound with use_qrm / use_rsh)");
@@ -253,6 +264,8 @@ int rmx_learn_rmax_bind(rmx_handle* h, int32_t threshold, double vi_delta, int v
   }
   if (h->host ? h->host->lam_on : h->learn.lam_on)
     return fail(RMX_E_STATE, "Q(lambda) trace lists are bound (rmx_learn_lambda_bind): unbind them before an R-max model");
+  if (h->host ? h->host->qrmax_on : h->learn.qrmax_on)
+    return fail(RMX_E_STATE, "a QR-max model is bound (rmx_learn_qrmax_bind): unbind it before an R-max model");
   const rmx::LearnParams& lp = h->host ? h->host->learn : h->learn.params;
   if (lp.use_rsh) return fail(RMX_E_INVALID, "R-max has no reward shaping (the learner was bound with use_rsh)");
   if (!lp.visits) return fail(RMX_E_INVALID, "R-max needs the visits table (it serves as s_a_counts)");
@@ -340,6 +353,143 @@ int rmx_learn_rmax_info(rmx_handle* h, int64_t* solves, int64_t* max_sweeps) {
   return RMX_OK;
 }
 
+int rmx_learn_qrmax_slots(const rmx_handle* h, int32_t* cap_full) {
+  if (!h || !cap_full) return fail(RMX_E_INVALID, "handle or cap_full is NULL");
+  int64_t s_max = 0;
+  const int rc = rmx_learn_states(h, &s_max);
+  if (rc) return rc;
+  if (s_max > INT32_MAX) return fail(RMX_E_INVALID, "S_max exceeds the int32 state indices of the QR-max model");
+  *cap_full = rmx::kQRMaxSlotsFull;
+  return RMX_OK;
+}
+
+int rmx_learn_qrmax_bind(rmx_handle* h, int32_t nsamples_te, int32_t nsamples_re, int32_t nsamples_tq,
+                         int32_t nsamples_rq, double vi_delta, int vi_delta_rel, int32_t max_iter, int32_t cap,
+                         uint8_t* known_tsqa, int32_t* n_tsa, int32_t* n_rsa, double* sum_rsa, int32_t* succ_idx,
+                         int32_t* succ_cnt, int32_t* n_tqs, int32_t* tq_next, int32_t* n_rqs, double* sum_rqs,
+                         uint8_t* final) {
+  if (!h) return fail(RMX_E_INVALID, "handle is NULL");
+  if (!(h->host ? h->host->learn_on : h->learn.on))
+    return fail(RMX_E_STATE, "no learner bound (rmx_learn_bind comes before rmx_learn_qrmax_bind)");
+  if (!known_tsqa) {  // back to Q-learning steps on the same tables
+    if (h->host)
+      h->host->qrmax_on = false;
+    else
+      h->learn.qrmax_on = false;
+    return RMX_OK;
+  }
+  if (h->host ? h->host->lam_on : h->learn.lam_on)
+    return fail(RMX_E_STATE, "Q(lambda) trace lists are bound (rmx_learn_lambda_bind): unbind them before a QR-max model");
+  if (h->host ? h->host->rmax_on : h->learn.rmax_on)
+    return fail(RMX_E_STATE, "an R-max model is bound (rmx_learn_rmax_bind): unbind it before a QR-max model");
+  const rmx::LearnParams& lp = h->host ? h->host->learn : h->learn.params;
+  if (lp.use_rsh) return fail(RMX_E_INVALID, "QR-max has no reward shaping (the learner was bound with use_rsh)");
+  if (!lp.visits) return fail(RMX_E_INVALID, "QR-max needs the visits table (it serves as nTSQA)");
+  if (!(lp.gamma < 1.0)) return fail(RMX_E_INVALID, "QR-max needs gamma < 1 (value iteration on the learned MDP)");
+  if (nsamples_te < 1 || nsamples_re < 1 || nsamples_tq < 1 || nsamples_rq < 1)
+    return fail(RMX_E_INVALID, "every threshold (nsamples_te / _re / _tq / _rq) must be >= 1");
+  if (!std::isfinite(vi_delta) || vi_delta <= 0.0) return fail(RMX_E_INVALID, "vi_delta must be finite and > 0");
+  if (max_iter < 1) return fail(RMX_E_INVALID, "max_iter must be >= 1");
+  int32_t cap_full = 0;
+  const int rc = rmx_learn_qrmax_slots(h, &cap_full);
+  if (rc) return rc;
+  if (cap < 1 || cap > cap_full) return fail(RMX_E_INVALID, "cap must be in [1, the full cap] (rmx_learn_qrmax_slots)");
+  if (!n_tsa || !n_rsa || !sum_rsa || !succ_idx || !succ_cnt || !n_tqs || !tq_next || !n_rqs || !sum_rqs || !final)
+    return fail(RMX_E_INVALID, "a model array is NULL");
+  auto mis = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+  if (mis(sum_rsa, 8) || mis(sum_rqs, 8) || mis(n_tsa, 4) || mis(n_rsa, 4) || mis(succ_idx, 4) || mis(succ_cnt, 4) ||
+      mis(n_tqs, 4) || mis(tq_next, 4) || mis(n_rqs, 4))
+    return fail(RMX_E_INVALID, "the model arrays must be aligned to their element types");
+  const int A = h->cfg.n_agents;
+  const int64_t N = h->cfg.n_envs, AN = (int64_t)A * N;
+  if (AN > INT32_MAX) return fail(RMX_E_INVALID, "A * N exceeds the int32 learner indices of the worklist");
+  rmx::QRMaxParams qp{};
+  qp.delta = vi_delta;
+  qp.delta_rel = vi_delta_rel ? 1 : 0;
+  qp.max_iter = max_iter;
+  qp.n_te = nsamples_te;
+  qp.n_re = nsamples_re;
+  qp.n_tq = nsamples_tq;
+  qp.n_rq = nsamples_rq;
+  qp.cap = cap;
+  qp.P = h->cfg.width * h->cfg.height;
+  qp.known_tsqa = known_tsqa;
+  qp.n_tsa = n_tsa;
+  qp.n_rsa = n_rsa;
+  qp.sum_rsa = sum_rsa;
+  qp.succ_idx = succ_idx;
+  qp.succ_cnt = succ_cnt;
+  qp.n_tqs = n_tqs;
+  qp.tq_next = tq_next;
+  qp.n_rqs = n_rqs;
+  qp.sum_rqs = sum_rqs;
+  qp.fin = final;
+  if (h->host) {
+    try {
+      h->host->qrmax_scratch.assign((size_t)lp.s_max, 0.0);
+    } catch (const std::exception& e) {
+      return fail(RMX_E_INVALID, std::string("rmx_learn_qrmax_bind: ") + e.what());
+    }
+    h->host->qrmax = qp;
+    h->host->qrmax_on = true;
+    h->host->qrmax_solves = h->host->qrmax_sweeps_max = h->host->qrmax_sweeps_total = 0;
+    return RMX_OK;
+  }
+  // the solve kernel keeps V of one learner double-buffered in LDS, 16 B per state: larger worlds are refused here
+  if (lp.s_max > rmx::kRMaxStatesMax)
+    return fail(RMX_E_INVALID, "S_max = " + std::to_string(lp.s_max) + " exceeds the " +
+                                   std::to_string((long long)rmx::kRMaxStatesMax) +
+                                   " states whose values the QR-max solve kernel holds in LDS (16 B per state)");
+  SYNC_END_OR_RETURN(h);
+  HIP_TRY(hipSetDevice(h->device), "hipSetDevice");
+  // the hand-over between the two kernels, one allocation: counters and statistics | worklist
+  const size_t off_list = 64, bytes = off_list + 4 * (size_t)AN;
+  (void)hipFree(h->learn.d_qrmax);
+  h->learn.d_qrmax = nullptr;
+  HIP_TRY(hipMalloc(&h->learn.d_qrmax, bytes), "QR-max worklist alloc");
+  HIP_TRY(hipMemset(h->learn.d_qrmax, 0, bytes), "QR-max worklist clear");
+  rmx::RMaxWork wk{};  // (recs and hdr stay NULL: no experience is handed over)
+  wk.count = reinterpret_cast<uint32_t*>(h->learn.d_qrmax);
+  wk.stats = reinterpret_cast<unsigned long long*>(h->learn.d_qrmax + 16);  // solves, longest solve, sweeps in all
+  wk.list = reinterpret_cast<int32_t*>(h->learn.d_qrmax + off_list);
+  wk.parity = 0;
+  for (int a = 0; a < A; ++a) wk.S[a] = h->cfg.width * h->cfg.height * h->enc_nq[a];
+  wk.N = N;
+  wk.n_learners = AN;
+  wk.err = h->d_err;
+  h->learn.qwork = wk;
+  h->learn.qrmax = qp;
+  h->learn.qrmax_grid = rmx::kRMaxGrid;
+  if (const char* g = std::getenv("RMX_QRMAX_GRID")) {  // tests: a grid smaller than a step's worklist
+    const long v = std::strtol(g, nullptr, 10);
+    if (v >= 1 && v <= 65536) h->learn.qrmax_grid = (int)v;
+  }
+  h->learn.qrmax_on = true;
+  return RMX_OK;
+}
+
+int rmx_learn_qrmax_info(rmx_handle* h, int64_t* solves, int64_t* max_sweeps, int64_t* total_sweeps) {
+  if (!h || !solves || !max_sweeps || !total_sweeps)
+    return fail(RMX_E_INVALID, "handle, solves, max_sweeps or total_sweeps is NULL");
+  if (!(h->host ? h->host->qrmax_on : h->learn.qrmax_on))
+    return fail(RMX_E_STATE, "no QR-max model bound (rmx_learn_qrmax_bind)");
+  if (h->host) {
+    *solves = h->host->qrmax_solves;
+    *max_sweeps = h->host->qrmax_sweeps_max;
+    *total_sweeps = h->host->qrmax_sweeps_total;
+    return RMX_OK;
+  }
+  SYNC_END_OR_RETURN(h);
+  HIP_TRY(hipSetDevice(h->device), "hipSetDevice");
+  HIP_TRY(hipDeviceSynchronize(), "sync");
+  unsigned long long st[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpy(st, h->learn.qwork.stats, sizeof(st), hipMemcpyDeviceToHost), "QR-max statistics copy");
+  *solves = (int64_t)st[0];
+  *max_sweeps = (int64_t)st[1];
+  *total_sweeps = (int64_t)st[2];
+  return RMX_OK;
+}
+
 int rmx_learn_eps_bind(rmx_handle* h, double* eps, double eps_end, double eps_decay) {
   if (!h) return fail(RMX_E_INVALID, "handle is NULL");
   if (!(h->host ? h->host->learn_on : h->learn.on))
@@ -405,6 +555,9 @@ int rmx_learn_run(rmx_handle* h, int32_t T, double epsilon, int flags, uint64_t 
   if (!(h->host ? h->host->learn_on : h->learn.on)) return fail(RMX_E_STATE, "no learner bound (rmx_learn_bind)");
   if (h->host ? h->host->rmax_on : h->learn.rmax_on)
     return fail(RMX_E_STATE, "rmx_learn_run does not serve R-max learners (one thread per env cannot run a "
+                             "workgroup-wide solve): loop rmx_learn_step_policy");
+  if (h->host ? h->host->qrmax_on : h->learn.qrmax_on)
+    return fail(RMX_E_STATE, "rmx_learn_run does not serve QR-max learners (one thread per env cannot run a "
                              "workgroup-wide solve): loop rmx_learn_step_policy");
   rmx::LearnCall lc{};
   lc.epsilon = epsilon;

@@ -145,6 +145,13 @@ struct rmx_handle {
     rmx::RMaxWork work{};
     unsigned char* d_rmax = nullptr;
     int rmax_grid = rmx::kRMaxGrid;
+    // rmx_learn_qrmax_bind: the learners are QR-max ones over the caller's model arrays (qrmax_on); the engine's own
+    // worklist between the step kernel and the solve kernel (one allocation, d_qrmax), the solve kernel's grid
+    rmx::QRMaxParams qrmax{};
+    bool qrmax_on = false;
+    rmx::RMaxWork qwork{};
+    unsigned char* d_qrmax = nullptr;
+    int qrmax_grid = rmx::kRMaxGrid;
   } learn;
 };
 

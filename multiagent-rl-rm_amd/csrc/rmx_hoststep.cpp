@@ -219,6 +219,27 @@ uint32_t HostEngine::rmax_agent(const LearnTables& T, const LearnStep& st, int a
   return bad;
 }
 
+uint32_t HostEngine::qrmax_agent(const LearnTables& T, const LearnStep& st, int a, int64_t e, int k) {
+  const QRMaxLearner L = qrmax_learner(learn, qrmax, (int64_t)a * cfg.n_envs + e);
+  uint32_t bad = 0;
+  bool fresh = false;
+  const int n = qrmax_n_exp(learn, T);
+  for (int j = 0; j < n; ++j) {
+    QRMaxExp x;
+    if (!qrmax_experience(learn, T, st, j, qrmax.P, x)) continue;
+    const int res = qrmax_update(qrmax, L, T.enc_nq, x, k);
+    if (res & kQRMaxFull) bad |= (uint32_t)kErrModelFull;
+    fresh = fresh || (res & kQRMaxNew);
+  }
+  if (fresh) {  // one solve behind the last experience of the agent-step
+    const int sweeps = qrmax_solve(qrmax, learn.gamma, L, T.enc_nq, qrmax_scratch.data());
+    ++qrmax_solves;
+    qrmax_sweeps_max = std::max<int64_t>(qrmax_sweeps_max, sweeps);
+    qrmax_sweeps_total += sweeps;
+  }
+  return bad;
+}
+
 void HostEngine::eps_decay(const uint8_t* mask) {
   const int64_t N = cfg.n_envs;
   for (int64_t e = 0; e < N; ++e) {
@@ -266,7 +287,7 @@ uint32_t HostEngine::step_kind(const int32_t* actions, int autoreset, bool hashe
       reset_regs(s, t, p);
       // a learn step's reset is learn_done_episode for every agent's learner: a policy step decays where it reads the
       // learner's epsilon below, a step on the caller's actions here (as the kernel)
-      if (lc && !lc->policy && eps.col && !rmax_on) learn_eps_reset(eps, A, N, e);
+      if (lc && !lc->policy && eps.col && !rmax_on && !qrmax_on) learn_eps_reset(eps, A, N, e);
       if (lc && lam_on)  // a learn step's reset clears the traces of every agent's learner
         for (int a = 0; a < A; ++a) lam.cnt[(int64_t)a * N + e] = 0;
       if (rng_on) {  // env.rng = default_rng(seed of the next episode)
@@ -286,6 +307,23 @@ uint32_t HostEngine::step_kind(const int32_t* actions, int autoreset, bool hashe
                                 ? learn.q + (((int64_t)a * N + e) * learn.s_max + st) * 4
                                 : none;
         // the learner's own epsilon with a schedule bound (decayed under RMX_LEARN_BEST too), else the call's
+        if (qrmax_on) {  // QR-max has no epsilon: the shuffle on every numpy call; a flat row picks, any other argmax
+          if (lc->policy == kLearnNumpy) {
+            const int64_t plane = (int64_t)A * N;
+            uint64_t* w = lc->rng + (int64_t)a * N + e;
+            const uint64_t w4 = w[4 * plane];
+            LearnRng r = {{w[0], w[plane], w[2 * plane], w[3 * plane]}, (uint32_t)(w4 >> 32), (uint32_t)w4};
+            act[a] = qrmax_policy_numpy(r, lc->best, row[0], row[1], row[2], row[3]);
+            w[0] = r.hi;
+            w[plane] = r.lo;
+            if (learn_rng_word4(r) != w4) w[4 * plane] = learn_rng_word4(r);
+          } else {
+            act[a] = rmax_policy(seed, t_global, cfg.n_envs_global, cfg.env_offset + e, A, a, lc->best, row[0], row[1],
+                                 row[2], row[3]);
+          }
+          if (lc->actions_out) lc->actions_out[(int64_t)a * N + e] = act[a];
+          continue;
+        }
         if (rmax_on) {  // R-max has no epsilon: a flat row draws, any other takes its first maximum
           if (lc->policy == kLearnNumpy && !lc->best) {
             if (rmax_row_flat(row[0], row[1], row[2], row[3])) {  // (no draw otherwise: the column is not touched)
@@ -369,7 +407,9 @@ uint32_t HostEngine::step_kind(const int32_t* actions, int autoreset, bool hashe
                               o[a].env_term,  o[a].term, o[a].trunc, o[a].renv};
         const int64_t base = ((int64_t)a * N + e) * learn.s_max * 4;
         double* va = learn.visits ? learn.visits + base : nullptr;
-        if (rmax_on)
+        if (qrmax_on)
+          bad |= qrmax_agent(T, st, a, e, act[a]);
+        else if (rmax_on)
           bad |= rmax_agent(T, st, a, e, act[a]);
         else if (lam_on)
           bad |= learn_lambda_agent(learn, lam, T, st, learn.q + base, va, act[a], mdp_states(a), a, N, e)

@@ -15,6 +15,7 @@
 #include "../../include/rmx.h"
 #include "rmx_host.h"
 #include "rmx_learn.h"
+#include "rmx_qrmax.h"
 #include "rmx_rmax.h"
 #include "rmx_rules.h"
 
@@ -85,6 +86,15 @@ struct HostEngine {
   int64_t rmax_solves = 0, rmax_sweeps_max = 0;  // solves so far, the longest one's sweeps (tests)
   // every experience of one agent-step in order, each crossing solved at once; kErrModelFull or 0
   uint32_t rmax_agent(const LearnTables& T, const LearnStep& st, int a, int64_t e, int k);
+  // rmx_learn_qrmax_bind: QR-max learners over the caller's model arrays (host pointers); the solve's scratch (v of
+  // S_max doubles).  A learn step's update is then qrmax_agent, its policy rmax_policy / qrmax_policy_numpy, and the
+  // epsilon column is left alone.
+  QRMaxParams qrmax{};
+  bool qrmax_on = false;
+  std::vector<double> qrmax_scratch;
+  int64_t qrmax_solves = 0, qrmax_sweeps_max = 0, qrmax_sweeps_total = 0;
+  // every experience of one agent-step in order, then one solve if any made something known; kErrModelFull or 0
+  uint32_t qrmax_agent(const LearnTables& T, const LearnStep& st, int a, int64_t e, int k);
   // learn_done_episode of every agent's learner of the masked envs (NULL: every env); a column must be bound
   void eps_decay(const uint8_t* mask);
   // cnt[a][e] = 0 for the masked envs (NULL: every env); nothing without Q(lambda) bound

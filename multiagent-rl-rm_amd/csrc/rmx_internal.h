@@ -9,6 +9,7 @@
 #include "../../include/rmx.h"
 #include "rmx_layout.h"
 #include "rmx_learn.h"
+#include "rmx_qrmax.h"
 #include "rmx_rmax.h"
 #include "rmx_rules.h"
 
@@ -393,6 +394,10 @@ hipError_t launch_learn_run_eps(const KParams& p, const LearnParams& lp, const L
 // crossing, then (lc.update) the solve kernel over the step's worklist, `grid` workgroups
 hipError_t launch_learn_rmax(const KParams& p, const LearnParams& lp, const LearnCall& lc, const RMaxParams& rp,
                              const RMaxWork& wk, int grid, int kind, size_t lds, hipStream_t st);
+// The QR-max learn step (rmx_learn_qrmax.hip): the step kernel with every learner's model update, then (lc.update) the
+// solve kernel over the step's worklist of learners with something newly known, `grid` workgroups
+hipError_t launch_learn_qrmax(const KParams& p, const LearnParams& lp, const LearnCall& lc, const QRMaxParams& qp,
+                              const RMaxWork& wk, int grid, int kind, size_t lds, hipStream_t st);
 // cnt[a][e] = 0 for every env of the device mask (NULL: every env)
 hipError_t launch_traces_clear(int32_t* cnt, const uint8_t* mask, int A, int64_t N, hipStream_t st);
 // rmx_learn_eps_decay: learn_done_episode of every agent's learner of every env of the device mask (NULL: every env)

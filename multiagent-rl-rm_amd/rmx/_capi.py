@@ -34,6 +34,7 @@ EXPORTS = (
     "rmx_learn_lambda_bind",
     "rmx_learn_traces_clear", "rmx_learn_run", "rmx_learn_eps_bind", "rmx_learn_eps_decay",
     "rmx_learn_rmax_slots", "rmx_learn_rmax_bind", "rmx_learn_rmax_info",
+    "rmx_learn_qrmax_slots", "rmx_learn_qrmax_bind", "rmx_learn_qrmax_info",
 )
 LEARN_UPDATE, LEARN_BEST, LEARN_NUMPY = 1, 2, 4  # RMX_LEARN_*
 LEARN_DYN_FIXED, LEARN_DYN_ENV = 0, 1  # rmx_learn_config.dynamics
@@ -64,7 +65,8 @@ HASHED_SOURCES = ("rmx_kernels.hip", "rmx_fast.hip", "rmx_fast_step.inc", "rmx_s
                   "rmx_comd.cpp", "rmx_build_info.cpp", "rmx_internal.h", "rmx_layout.h", "rmx_host.h", "rmx_device.h",
                   "rmx_generic.h", "rmx_comd.h", "rmx_hoststep.cpp", "rmx_hoststep.h", "rmx_learn.hip", "rmx_learn_run.hip", "rmx_learn.h",
                   "rmx_rules.h", "../../include/rmx.h",
-                  "Makefile", "rmx_learn_eps.hip", "rmx_learn_run_eps.hip", "rmx_rmax.h", "rmx_learn_rmax.hip")
+                  "Makefile", "rmx_learn_eps.hip", "rmx_learn_run_eps.hip", "rmx_rmax.h", "rmx_learn_rmax.hip",
+                  "rmx_qrmax.h", "rmx_learn_qrmax.hip")
 
 
 def source_hash(csrc: str = CSRC) -> str:
@@ -252,6 +254,9 @@ def load_library(path: str = None, check_source: bool = True):
         "rmx_learn_rmax_slots": (C.c_int, [vp, C.POINTER(C.c_int32)]),
         "rmx_learn_rmax_bind": (C.c_int, [vp, i32, C.c_double, C.c_int, i32, i32, vp, vp, vp]),
         "rmx_learn_rmax_info": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "rmx_learn_qrmax_slots": (C.c_int, [vp, C.POINTER(C.c_int32)]),
+        "rmx_learn_qrmax_bind": (C.c_int, [vp, i32, i32, i32, i32, C.c_double, C.c_int, i32, i32] + [vp] * 11),
+        "rmx_learn_qrmax_info": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

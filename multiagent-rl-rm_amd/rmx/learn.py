@@ -507,3 +507,139 @@ class VecRMax(VecQLearning):
         n, m = C.c_int64(), C.c_int64()
         _capi.check(self.lib.rmx_learn_rmax_info(self.env._h, C.byref(n), C.byref(m)), "rmx_learn_rmax_info")
         return int(n.value), int(m.value)
+
+
+class VecQRMax(VecQLearning):
+    """One QR-max learner per (env, agent): the reference's ``QRMax_v2`` (learning_algorithms/qrmax_v2.py) as
+    ``AgentRL.update_policy`` drives it, which is what the OfficeWorld runner's ``--algorithm QRMAX`` / ``QRMAXRM``
+    (``use_qrm``) build through ``create_qrmax`` (include/rmx.h, "QR-max learners").  QR-max is the R-max variant that
+    exploits the Reward Machine: it learns the environment model over grid positions only (``n_tsa``, ``n_rsa``,
+    ``sum_rsa`` ``[A, N, P, 4]`` and the successors of each (position, action) as lists ``succ_idx`` / ``succ_cnt``
+    ``[A, N, P, 4, cap]`` in first-seen order, ``P = W*H``), the RM model separately (``n_tqs``, ``tq_next``, ``n_rqs``,
+    ``sum_rqs`` ``[A, N, S_max]`` at the encoded ``(s', q)``), and takes ``(s, q, a)`` as known (``known_tsqa``) as soon
+    as both factors are, so one visit to a cell in any RM state teaches every RM state.  ``visits`` is the reference's
+    ``nTSQA``; ``final`` ``[A, N, S_max]`` marks the observed final states; ``q`` starts at ``max_reward * nQ /
+    (1 - gamma)`` with ``nQ = enc_nq[a]``, per agent.  An agent-step in which anything became known ends with one
+    value iteration (``vi_delta``, ``vi_delta_rel``, at most ``max_iter`` sweeps).  On a GPU env a learn step is the
+    step kernel plus a solve kernel that walks the learners with a solve pending (csrc/rmx_learn_qrmax.hip); a host env
+    runs the same functions in order.  Every table equals the reference's bit for bit, on slip worlds too.
+
+    ``step``, ``act_step``, ``run``, ``greedy`` and the generator accessors are ``VecQLearning``'s.  There is no
+    epsilon: ``act_step`` / ``run`` take none (passing one raises).  With ``reference_stream`` every call shuffles the
+    four actions on the learner's generator first, as the reference does; a flat row then picks from the shuffled list,
+    any other row takes its first maximum.  ``succ_cap`` (default: ``rmx_learn_qrmax_slots``, which cannot overflow) is
+    cap; a successor that finds its list full is dropped from the list (still counted) and ``env.check_errors()``
+    raises ``RuntimeError``.  No reset touches the model.  Not reproduced: ``noupdate_cnt`` and the early-stop return
+    value of ``update``; ``reset_VI``; ``tosolve_VI`` / ``learn_done_episode`` (never armed); ``save_environment`` /
+    ``load_environment`` (the model arrays are yours: copy them); the bookkeeping no computation reads (``nTSQAS``,
+    ``nTSQA_dict``, ``entrySQ_dict``, ``nRSQA``, ``nRSQASQ``, ``sumR``, ``pTSAS``); ``UCBVI``, ``OPSRL``."""
+
+    MODEL = ("known_tsqa", "n_tsa", "n_rsa", "sum_rsa", "succ_idx", "succ_cnt", "n_tqs", "tq_next", "n_rqs", "sum_rqs",
+             "final")
+
+    def __init__(self, env, gamma, nsamples_te=100, nsamples_re=100, nsamples_tq=1, nsamples_rq=1, max_reward=1.0,
+                 vi_delta=1e-4, vi_delta_rel=False, use_qrm=False, trunc_is_terminal=None, policy_seeds=None,
+                 succ_cap=None, max_iter=10000):
+        if not float(gamma) < 1.0:
+            raise ValueError("QR-max needs gamma < 1")
+        super().__init__(env, gamma, learning_rate=1.0, qtable_init=0.0, use_qrm=use_qrm, use_rsh=False,
+                         trunc_is_terminal=trunc_is_terminal, policy_seeds=policy_seeds)
+        self.learning_rate = None  # (QR-max has none; the Q-learning steps after unbind() run at rate 1)
+        tab = env.tables
+        for a in range(env.A):  # R_max = max_reward * nQ, per agent
+            self.q[a] = float(max_reward) * int(tab.enc_nq[a]) / (1.0 - float(gamma))
+        full = C.c_int32()
+        _capi.check(self.lib.rmx_learn_qrmax_slots(env._h, C.byref(full)), "rmx_learn_qrmax_slots")
+        self.succ_full = int(full.value)
+        self.succ_cap = self.succ_full if succ_cap is None else int(succ_cap)
+        self.nsamples_te, self.nsamples_re = int(nsamples_te), int(nsamples_re)
+        self.nsamples_tq, self.nsamples_rq = int(nsamples_tq), int(nsamples_rq)
+        self.max_reward = float(max_reward)
+        self.vi_delta, self.vi_delta_rel, self.max_iter = float(vi_delta), bool(vi_delta_rel), int(max_iter)
+        self.P = tab.width * tab.height
+        self.n_tsqa = self.visits
+        cap = max(self.succ_cap, 1)  # (a refused cap is refused by the bind below, not by the allocation)
+        sq, sa, s = (env.A, env.N, self.S_max, 4), (env.A, env.N, self.P, 4), (env.A, env.N, self.S_max)
+        spec = dict(known_tsqa=(sq, "uint8"), n_tsa=(sa, "int32"), n_rsa=(sa, "int32"), sum_rsa=(sa, "float64"),
+                    succ_idx=(sa + (cap,), "int32"), succ_cnt=(sa + (cap,), "int32"), n_tqs=(s, "int32"),
+                    tq_next=(s, "int32"), n_rqs=(s, "int32"), sum_rqs=(s, "float64"), final=(s, "uint8"))
+        if self.host:
+            arrays = {k: np.zeros(shape, dt) for k, (shape, dt) in spec.items()}
+        else:
+            t = env.torch
+            arrays = {k: t.zeros(shape, dtype=getattr(t, dt), device=env.device) for k, (shape, dt) in spec.items()}
+        self.bind_model(self.succ_cap, **arrays)
+
+    def _ptr(self, x):
+        return x.ctypes.data if self.host else x.data_ptr()
+
+    def bind_model(self, cap, **arrays):
+        """rmx_learn_qrmax_bind with the caller's own arrays, by the names of ``MODEL`` (numpy on a host env, tensors
+        or views on a GPU env)."""
+        if sorted(arrays) != sorted(self.MODEL):
+            raise ValueError(f"bind_model takes exactly the arrays {self.MODEL}")
+        _capi.check(self.lib.rmx_learn_qrmax_bind(self.env._h, self.nsamples_te, self.nsamples_re, self.nsamples_tq,
+                                                  self.nsamples_rq, self.vi_delta, int(self.vi_delta_rel),
+                                                  self.max_iter, int(cap), *[self._ptr(arrays[k]) for k in self.MODEL]),
+                    "rmx_learn_qrmax_bind")
+        for k in self.MODEL:
+            setattr(self, k, arrays[k])
+        self.succ_cap = int(cap)
+
+    def model(self):
+        """The bound model arrays by name (what ``bind_model`` takes)."""
+        return {k: getattr(self, k) for k in self.MODEL}
+
+    def unbind(self):
+        """Back to plain Q-learning steps on the same tables (``bind_model`` binds the model again)."""
+        _capi.check(self.lib.rmx_learn_qrmax_bind(self.env._h, 0, 0, 0, 0, 0.0, 0, 0, 0, *([None] * 11)),
+                    "rmx_learn_qrmax_bind")
+
+    def _epsilon_arg(self, epsilon):
+        if epsilon is not None:
+            raise ValueError("QR-max has no epsilon: epsilon must be None")
+        return 0.0
+
+    def run(self, T, epsilon=None, seed=None, t_global=None, best=False, learn=True, reference_stream=False,
+            actions_out=None):
+        """``T`` consecutive auto-resetting ``act_step``s (global steps ``t_global .. t_global + T - 1``), with the
+        result contract of ``VecQLearning.run``: the tables, the model, every column and the generators end as the T
+        single steps leave them, because they ARE the T single steps: rmx_learn_run does not serve QR-max (one thread
+        per env cannot run a workgroup-wide solve), so this loops ``act_step`` in Python, one call and at most two
+        launches per step.  ``actions_out``: a contiguous int32 ``[T, A, N]`` tensor (an array on a host env)."""
+        return VecRMax.run(self, T, epsilon, seed, t_global, best, learn, reference_stream, actions_out)
+
+    def _np(self, x):
+        if self.host:
+            return x
+        self.env.sync_end()
+        return x.cpu().numpy()
+
+    def known(self):
+        """The reference's ``known(s, q, a)``: ``knownTSA[s, a] and knownRSA[s, a] and knownTSQA[s, q, a]`` as
+        ``[A, N, S_max, 4]`` bool (numpy); with final states excluded, the entries value iteration writes."""
+        tab = self.env.tables
+        env_known = (self._np(self.n_tsa) >= self.nsamples_te) & (self._np(self.n_rsa) >= self.nsamples_re)
+        out = self._np(self.known_tsqa) != 0
+        for a in range(self.env.A):
+            nq = int(tab.enc_nq[a])
+            out[a, :, :self.P * nq] &= np.repeat(env_known[a], nq, axis=1)
+            out[a, :, self.P * nq:] = False
+        return out
+
+    def env_transitions(self):
+        """The reference's dense ``nTSAS`` rebuilt from the lists: [A, N, P, 4, P] float64 (numpy)."""
+        idx, cnt = self._np(self.succ_idx), self._np(self.succ_cnt)
+        A, N, P, _, cap = cnt.shape
+        out = np.zeros((A, N, P, 4, P), np.float64)
+        a, e, s, k, j = np.nonzero(cnt)
+        out[a, e, s, k, idx[a, e, s, k, j]] = cnt[a, e, s, k, j]
+        return out
+
+    def solve_info(self):
+        """``(solves, max_sweeps, total_sweeps)``: the solves made since the model was bound, the sweeps of the
+        longest one and the sweeps of all of them.  Synchronises a GPU env."""
+        n, m, s = C.c_int64(), C.c_int64(), C.c_int64()
+        _capi.check(self.lib.rmx_learn_qrmax_info(self.env._h, C.byref(n), C.byref(m), C.byref(s)),
+                    "rmx_learn_qrmax_info")
+        return int(n.value), int(m.value), int(s.value)
