@@ -462,7 +462,8 @@ int rmx_step_info(const rmx_handle* h, int64_t* out, int32_t n);
  * work: a NULL handle / config / q, gamma or learning_rate not finite or negative, no enc_nq, use_qrm with
  * n_qrm_max == 0, use_rsh without use_qrm or phi, 1/visits without visits, a dynamics value other than the two below,
  * cfg.stochastic / cfg.random_starts under RMX_LEARN_DYN_FIXED, epsilon outside [0, 1], unknown flags.  A learn step before rmx_bind or rmx_learn_bind: RMX_E_STATE.
- * Not served: rmx_step_seq windows (learn steps are stream launches; T of them in one launch: rmx_learn_run below),
+ * Not served: rmx_step_seq windows (learn steps are stream launches; T of them in one launch: rmx_learn_run below,
+ * rmx_learn_model_run for R-max and QR-max learners),
  * the dict API, the tables in rmx_get_state (they are the caller's).
  * Runs (rmx_learn_run): exactly T consecutive calls of rmx_learn_step_policy(h, epsilon, flags, seed, t_global + k,
  * autoreset = 1, actions_out ? actions_out + k*A*N : NULL, stream), k = 0..T-1, in ONE launch on a device handle
@@ -647,9 +648,10 @@ int rmx_learn_eps_decay(rmx_handle* h, const uint8_t* env_mask /* NULL: all */, 
  * RMX_E_MODEL (an invalid action or a full trace list reported at the same time wins).  Nothing is written at or past
  * slot cap.
  * None of the arrays is part of rmx_get_state, and no reset touches them: env.reset() does nothing to an RMax.
- * rmx_learn_run on a handle with R-max bound: RMX_E_STATE (one thread per env cannot run a workgroup-wide solve); a
- * caller loops rmx_learn_step_policy.  A device handle keeps the values of the learner being solved in LDS, 16 B per
- * state: S_max above 4064 is refused at bind (a host handle has no such bound).
+ * rmx_learn_run on a handle with R-max bound: RMX_E_STATE (one thread per env cannot run a workgroup-wide solve);
+ * rmx_learn_model_run below runs T steps of such a handle in one launch, one wave per env.  A device handle keeps the
+ * values of the learner being solved in LDS, 16 B per state: S_max above 4064 is refused at bind (a host handle has no
+ * such bound).
  * rmx_learn_rmax_bind: a NULL rsum unbinds (Q-learning steps on the same tables again); a later rmx_learn_bind drops
  * the binding; refused (RMX_E_STATE) while Q(lambda) lists are bound, as rmx_learn_lambda_bind is while a model is
  * bound, and before rmx_learn_bind.  RMX_E_INVALID with a message, before any device work: threshold < 1, vi_delta not
@@ -719,8 +721,9 @@ int rmx_learn_rmax_info(rmx_handle* h, int64_t* solves, int64_t* max_sweeps);
  * may bind fewer.  A successor that finds its list full is still counted in n_tsa, its entry is dropped, and the
  * error word gets the bit rmx_check_errors reports as RMX_E_MODEL.  Nothing is written at or past slot cap.
  * None of the arrays is part of rmx_get_state, and no reset touches them.  rmx_learn_run on a handle with QR-max
- * bound: RMX_E_STATE; a caller loops rmx_learn_step_policy.  A device handle keeps the values of the learner being
- * solved in LDS, 16 B per state: S_max above 4064 is refused at bind (a host handle has no such bound).
+ * bound: RMX_E_STATE; rmx_learn_model_run below runs T steps of such a handle in one launch.  A device handle keeps
+ * the values of the learner being solved in LDS, 16 B per state: S_max above 4064 is refused at bind (a host handle
+ * has no such bound).
  * rmx_learn_qrmax_bind: a NULL known_tsqa unbinds (Q-learning steps on the same tables again); a later rmx_learn_bind
  * drops the binding; refused (RMX_E_STATE) while Q(lambda) lists or an R-max model are bound, as those binds are while
  * a QR-max model is bound, and before rmx_learn_bind.  RMX_E_INVALID with a message, before any device work: a
@@ -738,6 +741,39 @@ int rmx_learn_qrmax_bind(rmx_handle* h, int32_t nsamples_te, int32_t nsamples_re
                          int32_t* succ_cnt, int32_t* n_tqs, int32_t* tq_next, int32_t* n_rqs, double* sum_rqs,
                          uint8_t* final);
 int rmx_learn_qrmax_info(rmx_handle* h, int64_t* solves, int64_t* max_sweeps, int64_t* total_sweeps);
+
+/* ---- runs of R-max and QR-max learners: T learn steps in one launch, one wave per env ----------------------------
+ * rmx_learn_model_run on a handle with an R-max or a QR-max model bound: exactly T consecutive calls of
+ * rmx_learn_step_policy(h, 0, flags, seed, t_global + k, autoreset = 1, actions_out ? actions_out + k*A*N : NULL,
+ * stream), k = 0..T-1.  There is no epsilon (the model learners have none); the flags are rmx_learn_run's
+ * (RMX_LEARN_UPDATE, RMX_LEARN_BEST, RMX_LEARN_NUMPY); auto-reset is always on; a run on the caller's own actions is
+ * not served.
+ * A device handle: ONE launch of one-wave workgroups, workgroup e owns env e (rmx_learn_rmax_run.hip,
+ * rmx_learn_qrmax_run.hip).  Lane 0 of the wave is the one thread rmx_learn_run gives an env: state, t, the env
+ * generator and the episode count stay in its registers over the T steps and the columns are stored once at the end;
+ * it chooses the actions, steps the env and applies the model updates.  Every solve runs on all 64 lanes at the place
+ * the reference has it: R-max at the crossing, before the next experience of the same agent-step (several crossings
+ * in one agent-step: several solves); QR-max once behind the agent-step's last experience when anything became known.
+ * No worklist, no record buffer and no second launch; envs never interact, so nothing synchronises across waves.
+ * The staged tables and the solve's values (16 B per state) share the LDS of a plain launch, 64 KiB, 512 B of it
+ * left to the kernel's own words.  Where the handle's table blob plus 16*S_max bytes exceed that, the call issues the
+ * same T steps as T two-launch learn steps on the caller's stream instead: it never refuses a bound model.
+ * After the call everything is as the T single steps leave it, bit for bit: every state column, the output columns
+ * (the LAST step's), q, visits and every model array, the learners' generator column, the env generator and episode
+ * columns, the solve statistics (rmx_learn_rmax_info / rmx_learn_qrmax_info) and the error word (the same
+ * RMX_E_MODEL when a bound cap overflows).  Episode statistics: the integer ones are equal; a device handle sums the
+ * returns per env over the run, so the return sum is associated differently from T single steps and agrees to
+ * rounding.  A host handle runs the T steps one after the other: everything is equal there, the return sum too.
+ * RMX_E_INVALID: a NULL handle, T < 1 or T > RMX_LEARN_MODEL_RUN_MAX, unknown flags.  RMX_E_STATE: before rmx_bind or
+ * rmx_learn_bind; no model bound (rmx_learn_run is the entry for such handles); RMX_LEARN_NUMPY with no column bound.
+ * Each with a message, before any device work.
+ * RMX_LEARN_MODEL_RUN_MAX keeps one launch bounded, as RMX_LEARN_RUN_MAX does, but a model learner's worst step is
+ * far slower than a Q-learning one: the slowest step measured is 11.4 ms (the first steps of a fresh R-max model at
+ * threshold 1 with 65,536 envs, where almost every learner solves in every step).  256 such steps are about 3 s, and
+ * still a few seconds if the fused kernel is twice as slow there. */
+#define RMX_LEARN_MODEL_RUN_MAX 256
+int rmx_learn_model_run(rmx_handle* h, int32_t T, int flags, uint64_t seed, int64_t t_global,
+                        int32_t* actions_out /* [T][A][N] or NULL */, void* hip_stream);
 
 /* Synchronise and report kernel-side errors (e.g. RMX_E_ACTION), then clear them. */
 int rmx_check_errors(rmx_handle* h);

@@ -555,10 +555,10 @@ int rmx_learn_run(rmx_handle* h, int32_t T, double epsilon, int flags, uint64_t 
   if (!(h->host ? h->host->learn_on : h->learn.on)) return fail(RMX_E_STATE, "no learner bound (rmx_learn_bind)");
   if (h->host ? h->host->rmax_on : h->learn.rmax_on)
     return fail(RMX_E_STATE, "rmx_learn_run does not serve R-max learners (one thread per env cannot run a "
-                             "workgroup-wide solve): loop rmx_learn_step_policy");
+                             "workgroup-wide solve): rmx_learn_model_run runs them, one wave per env");
   if (h->host ? h->host->qrmax_on : h->learn.qrmax_on)
     return fail(RMX_E_STATE, "rmx_learn_run does not serve QR-max learners (one thread per env cannot run a "
-                             "workgroup-wide solve): loop rmx_learn_step_policy");
+                             "workgroup-wide solve): rmx_learn_model_run runs them, one wave per env");
   rmx::LearnCall lc{};
   lc.epsilon = epsilon;
   lc.policy = (flags & RMX_LEARN_NUMPY) ? rmx::kLearnNumpy : rmx::kLearnHash;
@@ -588,6 +588,73 @@ int rmx_learn_run(rmx_handle* h, int32_t T, double epsilon, int flags, uint64_t 
                                 h->learn.eps.col ? &h->learn.eps : nullptr, T, h->cfg.kind, h->tables_bytes,
                                 as_stream(stream)),
           "learn run launch");
+  return RMX_OK;
+}
+
+int rmx_learn_model_run(rmx_handle* h, int32_t T, int flags, uint64_t seed, int64_t t_global, int32_t* actions_out,
+                        void* stream) {
+  if (!h) return fail(RMX_E_INVALID, "handle is NULL");
+  if (T < 1 || T > RMX_LEARN_MODEL_RUN_MAX) return fail(RMX_E_INVALID, "T must be in [1, RMX_LEARN_MODEL_RUN_MAX]");
+  if (flags & ~(RMX_LEARN_UPDATE | RMX_LEARN_BEST | RMX_LEARN_NUMPY)) return fail(RMX_E_INVALID, "unknown learn step flags");
+  if (!h->bound) return fail(RMX_E_STATE, "buffers not bound (rmx_bind)");
+  if (!(h->host ? h->host->learn_on : h->learn.on)) return fail(RMX_E_STATE, "no learner bound (rmx_learn_bind)");
+  const bool rmax = h->host ? h->host->rmax_on : h->learn.rmax_on;
+  const bool qrmax = h->host ? h->host->qrmax_on : h->learn.qrmax_on;
+  if (!rmax && !qrmax)
+    return fail(RMX_E_STATE, "rmx_learn_model_run serves R-max and QR-max learners (rmx_learn_rmax_bind / "
+                             "rmx_learn_qrmax_bind): no model is bound; rmx_learn_run is the entry for such handles");
+  rmx::LearnCall lc{};
+  lc.policy = (flags & RMX_LEARN_NUMPY) ? rmx::kLearnNumpy : rmx::kLearnHash;
+  lc.update = (flags & RMX_LEARN_UPDATE) ? 1 : 0;
+  lc.best = (flags & RMX_LEARN_BEST) ? 1 : 0;
+  lc.actions_out = actions_out;
+  if (lc.policy == rmx::kLearnNumpy) {
+    lc.rng = h->host ? h->host->learn_rng : h->learn.rng;
+    if (!lc.rng) return fail(RMX_E_STATE, "RMX_LEARN_NUMPY needs a generator column (rmx_learn_rng_bind)");
+  }
+  const int64_t AN = (int64_t)h->cfg.n_agents * h->cfg.n_envs;
+  if (h->host) {  // the same T steps, one after the other
+    for (int32_t k = 0; k < T; ++k) {
+      h->host->step(nullptr, 1, false, seed, t_global + k, nullptr, &lc);
+      if (lc.actions_out) lc.actions_out += AN;
+    }
+    return RMX_OK;
+  }
+  SYNC_END_OR_RETURN(h);
+  HIP_TRY(hipSetDevice(h->device), "hipSetDevice");
+  rmx::KParams p = base_params(h);
+  p.actions = nullptr;
+  p.seed = seed;
+  p.t_global = t_global;
+  p.autoreset = 1;
+  const size_t lds = rmx::model_run_lds(h->tables_bytes, h->learn.params.s_max);
+  if (lds <= rmx::kModelRunLdsMax) {  // one launch: one wave per env, the solves in place
+    if (qrmax)
+      HIP_TRY(rmx::launch_qrmax_run(p, h->learn.params, lc, h->learn.qrmax, h->learn.qwork, T, h->cfg.kind, lds,
+                                    as_stream(stream)),
+              "QR-max learn run launch");
+    else
+      HIP_TRY(rmx::launch_rmax_run(p, h->learn.params, lc, h->learn.rmax, h->learn.work, T, h->cfg.kind, lds,
+                                   as_stream(stream)),
+              "R-max learn run launch");
+    return RMX_OK;
+  }
+  // the tables and v do not fit in the LDS of a plain launch together: the same T steps as T two-launch steps
+  for (int32_t k = 0; k < T; ++k) {
+    p.t_global = t_global + k;
+    if (qrmax) {
+      HIP_TRY(rmx::launch_learn_qrmax(p, h->learn.params, lc, h->learn.qrmax, h->learn.qwork, h->learn.qrmax_grid,
+                                      h->cfg.kind, h->tables_bytes, as_stream(stream)),
+              "QR-max learn step launch");
+      if (lc.update) h->learn.qwork.parity ^= 1;  // (the solve kernel has zeroed the other list's length)
+    } else {
+      HIP_TRY(rmx::launch_learn_rmax(p, h->learn.params, lc, h->learn.rmax, h->learn.work, h->learn.rmax_grid,
+                                     h->cfg.kind, h->tables_bytes, as_stream(stream)),
+              "R-max learn step launch");
+      if (lc.update) h->learn.work.parity ^= 1;  // (the solve kernel has zeroed the other list's length)
+    }
+    if (lc.actions_out) lc.actions_out += AN;
+  }
   return RMX_OK;
 }
 

@@ -398,6 +398,18 @@ hipError_t launch_learn_rmax(const KParams& p, const LearnParams& lp, const Lear
 // solve kernel over the step's worklist of learners with something newly known, `grid` workgroups
 hipError_t launch_learn_qrmax(const KParams& p, const LearnParams& lp, const LearnCall& lc, const QRMaxParams& qp,
                               const RMaxWork& wk, int grid, int kind, size_t lds, hipStream_t st);
+// T consecutive auto-reset R-max / QR-max learn steps in one launch, one wave per env (rmx_learn_rmax_run.hip,
+// rmx_learn_qrmax_run.hip).  lds = model_run_lds(...): the staged tables, then the solve's double-buffered v; a world
+// whose sum exceeds kModelRunLdsMax is not launched (rmx_learn_model_run steps it): the 64 KiB of a plain launch, 512 B
+// of it left to the kernel's own words as in kRMaxStatesMax (the workgroup votes of the solve take 256 B)
+enum : size_t { kModelRunLdsMax = 65536 - 512 };
+inline size_t model_run_lds(size_t tables_bytes, int64_t s_max) {
+  return ((tables_bytes + 15) & ~(size_t)15) + 16 * (size_t)s_max;
+}
+hipError_t launch_rmax_run(const KParams& p, const LearnParams& lp, const LearnCall& lc, const RMaxParams& rp,
+                           const RMaxWork& wk, int32_t T, int kind, size_t lds, hipStream_t st);
+hipError_t launch_qrmax_run(const KParams& p, const LearnParams& lp, const LearnCall& lc, const QRMaxParams& qp,
+                            const RMaxWork& wk, int32_t T, int kind, size_t lds, hipStream_t st);
 // cnt[a][e] = 0 for every env of the device mask (NULL: every env)
 hipError_t launch_traces_clear(int32_t* cnt, const uint8_t* mask, int A, int64_t N, hipStream_t st);
 // rmx_learn_eps_decay: learn_done_episode of every agent's learner of every env of the device mask (NULL: every env)

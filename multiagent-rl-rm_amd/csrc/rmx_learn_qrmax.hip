@@ -9,7 +9,8 @@
 // experience is handed over.
 //
 // qrmax_solve_kernel: a fixed grid of one-wave workgroups walks the worklist by grid stride and leaves at once when it
-// is empty.  A workgroup solves one learner at a time: the rows of final states are zeroed, V = max_a Q double-buffered
+// is empty.  A workgroup solves one learner at a time (qrmax_solve_wg, rmx_model_solve.h, shared with the fused runs):
+// the rows of final states are zeroed, V = max_a Q double-buffered
 // in LDS (16 B per state), the lanes stride over (s, q, a).  Each entry of a sweep reads V of the sweep before and its
 // own old value only, so a sweep is ONE pass: back up, store in place, leave the next sweep's V in the other buffer
 // (the four lanes of a state exchange their entries by wave shuffle) and vote on cdelta > VI_delta.  The environment
@@ -25,6 +26,7 @@
 #include "rmx_generic.h"
 #include "rmx_internal.h"
 #include "rmx_learn.h"
+#include "rmx_model_solve.h"
 #include "rmx_qrmax.h"
 
 namespace rmx {
@@ -181,57 +183,6 @@ __global__ void __launch_bounds__(256) qrmax_step_kernel(KParams p, LearnParams 
     if ((threadIdx.x & 63) == 0) atomicOr(p.err, kErrModelFull);
   }
   wave_flush_slot(p.slab, slot, ls, __any(done));
-}
-
-// One solve of learner M (nQ RM states, S = P * nQ rows) by the whole workgroup (qrmax_solve, rmx_qrmax.h, is its
-// sequential statement).  v: [2][s_max] in LDS.  Returns the sweeps made; every thread has passed a barrier behind the
-// last store.
-__device__ int qrmax_solve_wg(const QRMaxParams& qp, double gamma, const QRMaxLearner& M, int32_t nQ, double* v,
-                              int64_t s_max) {
-  static_assert(kRMaxBlock % 4 == 0 && kRMaxBlock <= 64, "a state's four entries sit in four adjacent lanes of a wave");
-  const int tid = (int)threadIdx.x;
-  const int64_t S = (int64_t)qp.P * nQ, S4 = S * 4;
-  for (int64_t n = tid; n < S; n += kRMaxBlock) {  // final rows become zero here, not when they were marked
-    double2* row = reinterpret_cast<double2*>(M.q + n * 4);
-    double m = 0.0;
-    if (M.fin[n]) {
-      row[0] = row[1] = make_double2(0.0, 0.0);
-    } else {
-      const double2 lo = row[0], hi = row[1];
-      m = learn_max4(lo.x, lo.y, hi.x, hi.y);
-    }
-    v[n] = m;
-  }
-  __syncthreads();
-  int cur = 0, it = 0;
-  int more = 1.0 > qp.delta ? 1 : 0;  // delta = 1.0 before the first sweep
-  while (more && it < qp.max_iter) {
-    const double* vc = v + (int64_t)cur * s_max;
-    double* vn = v + (int64_t)(cur ^ 1) * s_max;
-    int moved = 0;
-    for (int64_t base = 0; base < S4; base += kRMaxBlock) {  // (a uniform trip count: every lane takes the shuffles)
-      const int64_t i = base + tid;
-      double val = 0.0;
-      if (i < S4) {
-        val = M.q[i];
-        const int64_t sq = i >> 2;
-        const int64_t sa = (sq / nQ) * 4 + (i & 3);
-        if (qrmax_solved_entry(qp, M, i, sa)) {
-          const double nw = qrmax_backup(qp, gamma, M, nQ, (int32_t)(sq % nQ), sa, vc);
-          if (qrmax_delta(nw, val, qp.delta_rel) > qp.delta) moved = 1;
-          M.q[i] = nw;
-          val = nw;
-        }
-      }
-      const int l0 = tid & ~3;
-      const double a0 = __shfl(val, l0), a1 = __shfl(val, l0 + 1), a2 = __shfl(val, l0 + 2), a3 = __shfl(val, l0 + 3);
-      if ((tid & 3) == 0 && i < S4) vn[i >> 2] = learn_max4(a0, a1, a2, a3);
-    }
-    more = __syncthreads_or(moved);
-    cur ^= 1;
-    ++it;
-  }
-  return it;
 }
 
 __global__ void __launch_bounds__(kRMaxBlock) qrmax_solve_kernel(LearnParams lp, QRMaxParams qp, RMaxWork wk) {

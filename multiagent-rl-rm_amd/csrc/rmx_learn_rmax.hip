@@ -10,7 +10,8 @@
 // unapplied, and the learner is appended to the step's worklist with one atomic add.
 //
 // rmax_solve_kernel: a fixed grid of one-wave workgroups walks the worklist by grid stride and leaves at once when it
-// is empty.  A workgroup solves one learner at a time: v = max_a q double-buffered in LDS (16 B per state), the lanes
+// is empty.  A workgroup solves one learner at a time (rmax_solve_wg, rmx_model_solve.h, shared with the fused runs):
+// v = max_a q double-buffered in LDS (16 B per state), the lanes
 // stride over (s, k), a sweep is a test pass (every masked entry's backup against its q; one vote across the
 // workgroup; nothing has been written when the vote says converged) and, if it has not converged, a write pass that
 // recomputes the backup from the same v, stores it and leaves the next sweep's v in the other buffer (the four lanes
@@ -27,6 +28,7 @@
 #include "rmx_generic.h"
 #include "rmx_internal.h"
 #include "rmx_learn.h"
+#include "rmx_model_solve.h"
 #include "rmx_rmax.h"
 
 namespace rmx {
@@ -196,62 +198,6 @@ __global__ void __launch_bounds__(256) rmax_step_kernel(KParams p, LearnParams l
     if ((threadIdx.x & 63) == 0) atomicOr(p.err, kErrModelFull);
   }
   wave_flush_slot(p.slab, slot, ls, __any(done));
-}
-
-// One solve of learner M over its S rows by the whole workgroup (rmax_solve, rmx_rmax.h, is its sequential statement).
-// v: [2][s_max] in LDS.  Returns the sweeps made; every thread has passed a barrier behind the last store.
-__device__ int rmax_solve_wg(const RMaxParams& rp, double gamma, const RMaxLearner& M, int64_t S, double* v,
-                             int64_t s_max) {
-  static_assert(kRMaxBlock % 4 == 0 && kRMaxBlock <= 64, "a state's four entries sit in four adjacent lanes of a wave");
-  const int tid = (int)threadIdx.x;
-  const int64_t S4 = S * 4;
-  const double thr = (double)rp.threshold;
-  int cur = 0;
-  for (int64_t n = tid; n < S; n += kRMaxBlock) {
-    double row[4];
-    learn_load_row(M.q + n * 4, row);
-    v[n] = learn_max4(row[0], row[1], row[2], row[3]);
-  }
-  __syncthreads();
-  int it = 0;
-  while (it < rp.max_iter) {
-    ++it;
-    const double* vc = v + (int64_t)cur * s_max;
-    double* vn = v + (int64_t)(cur ^ 1) * s_max;
-    // the test pass: nothing is written
-    int conv = 1;
-    for (int64_t base = 0; base < S4; base += kRMaxBlock) {
-      const int64_t i = base + tid;
-      if (i < S4) {
-        const double c = M.counts[i];
-        if (c >= thr) {
-          const double nw = rmax_backup(gamma, rp.cap, M.rsum[i], c, M.idx + i * rp.cap, M.cnt + i * rp.cap, vc);
-          conv &= rmax_converged(M.q[i], nw, rp.delta, rp.delta_rel) ? 1 : 0;
-        }
-      }
-    }
-    if (__syncthreads_and(conv)) break;
-    // the write pass: the same backups from the same v, and the next sweep's v into the other buffer
-    for (int64_t base = 0; base < S4; base += kRMaxBlock) {  // (a uniform trip count: every lane takes the shuffles)
-      const int64_t i = base + tid;
-      double val = 0.0;
-      if (i < S4) {
-        const double c = M.counts[i];
-        if (c >= thr) {
-          val = rmax_backup(gamma, rp.cap, M.rsum[i], c, M.idx + i * rp.cap, M.cnt + i * rp.cap, vc);
-          M.q[i] = val;
-        } else {
-          val = M.q[i];
-        }
-      }
-      const int l0 = tid & ~3;
-      const double a0 = __shfl(val, l0), a1 = __shfl(val, l0 + 1), a2 = __shfl(val, l0 + 2), a3 = __shfl(val, l0 + 3);
-      if ((tid & 3) == 0 && i < S4) vn[i >> 2] = learn_max4(a0, a1, a2, a3);
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
-  return it;
 }
 
 __global__ void __launch_bounds__(kRMaxBlock) rmax_solve_kernel(LearnParams lp, RMaxParams rp, RMaxWork wk) {

@@ -34,11 +34,12 @@ EXPORTS = (
     "rmx_learn_lambda_bind",
     "rmx_learn_traces_clear", "rmx_learn_run", "rmx_learn_eps_bind", "rmx_learn_eps_decay",
     "rmx_learn_rmax_slots", "rmx_learn_rmax_bind", "rmx_learn_rmax_info",
-    "rmx_learn_qrmax_slots", "rmx_learn_qrmax_bind", "rmx_learn_qrmax_info",
+    "rmx_learn_qrmax_slots", "rmx_learn_qrmax_bind", "rmx_learn_qrmax_info", "rmx_learn_model_run",
 )
 LEARN_UPDATE, LEARN_BEST, LEARN_NUMPY = 1, 2, 4  # RMX_LEARN_*
 LEARN_DYN_FIXED, LEARN_DYN_ENV = 0, 1  # rmx_learn_config.dynamics
 LEARN_RUN_MAX = 4096  # RMX_LEARN_RUN_MAX
+LEARN_MODEL_RUN_MAX = 256  # RMX_LEARN_MODEL_RUN_MAX
 SYNC_MAX_ENVS = 256  # RMX_SYNC_MAX_ENVS
 QUEUE_INFO_N = 7  # RMX_QUEUE_INFO_N
 QUEUE_STATES = ("unused", "ready", "unavailable", "retired")  # RMX_QUEUE_*
@@ -66,7 +67,8 @@ HASHED_SOURCES = ("rmx_kernels.hip", "rmx_fast.hip", "rmx_fast_step.inc", "rmx_s
                   "rmx_generic.h", "rmx_comd.h", "rmx_hoststep.cpp", "rmx_hoststep.h", "rmx_learn.hip", "rmx_learn_run.hip", "rmx_learn.h",
                   "rmx_rules.h", "../../include/rmx.h",
                   "Makefile", "rmx_learn_eps.hip", "rmx_learn_run_eps.hip", "rmx_rmax.h", "rmx_learn_rmax.hip",
-                  "rmx_qrmax.h", "rmx_learn_qrmax.hip")
+                  "rmx_qrmax.h", "rmx_learn_qrmax.hip", "rmx_model_solve.h", "rmx_learn_rmax_run.hip",
+                  "rmx_learn_qrmax_run.hip")
 
 
 def source_hash(csrc: str = CSRC) -> str:
@@ -251,6 +253,7 @@ def load_library(path: str = None, check_source: bool = True):
         "rmx_learn_traces_clear": (C.c_int, [vp, vp, vp]),
         "rmx_learn_eps_bind": (C.c_int, [vp, vp, C.c_double, C.c_double]),
         "rmx_learn_eps_decay": (C.c_int, [vp, vp, vp]),
+        "rmx_learn_model_run": (C.c_int, [vp, C.c_int32, C.c_int, u64, i64, vp, vp]),
         "rmx_learn_rmax_slots": (C.c_int, [vp, C.POINTER(C.c_int32)]),
         "rmx_learn_rmax_bind": (C.c_int, [vp, i32, C.c_double, C.c_int, i32, i32, vp, vp, vp]),
         "rmx_learn_rmax_info": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

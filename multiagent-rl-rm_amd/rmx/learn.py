@@ -399,9 +399,10 @@ class VecRMax(VecQLearning):
     ``[A, N, S_max, 4, cap]`` int32 in first-seen order; ``q`` starts at ``max_reward / (1 - gamma)``.  The observation
     that brings a pair to ``s_a_threshold`` solves the learner's MDP by value iteration at once (``vi_delta``,
     ``vi_delta_rel``, at most ``max_iter`` sweeps).  On a GPU env a learn step is the step kernel plus a solve kernel
-    that walks the learners with a solve pending (csrc/rmx_learn_rmax.hip); a host env runs the same functions in order.
+    that walks the learners with a solve pending (csrc/rmx_learn_rmax.hip), and ``run(T)`` is one launch in which a
+    wave per env steps and solves in place (csrc/rmx_learn_rmax_run.hip); a host env runs the same functions in order.
 
-    ``step``, ``act_step``, ``run``, ``greedy`` and the generator accessors are ``VecQLearning``'s.  There is no
+    ``step``, ``act_step``, ``greedy`` and the generator accessors are ``VecQLearning``'s.  There is no
     epsilon: ``act_step`` / ``run`` take none (passing one raises); a flat row draws one of the four actions, any
     other row takes its first maximum.  ``succ_cap`` (default: ``rmx_learn_rmax_slots``, which cannot overflow) is
     cap; a successor that finds its list full is dropped from the list (still counted) and ``env.check_errors()``
@@ -455,31 +456,60 @@ class VecRMax(VecQLearning):
         return 0.0
 
     def run(self, T, epsilon=None, seed=None, t_global=None, best=False, learn=True, reference_stream=False,
-            actions_out=None):
+            actions_out=None, fused=True):
         """``T`` consecutive auto-resetting ``act_step``s (global steps ``t_global .. t_global + T - 1``), with the
-        result contract of ``VecQLearning.run``: the tables, the model, every column and the generators end as the T
-        single steps leave them, because they ARE the T single steps: rmx_learn_run does not serve R-max (one thread
-        per env cannot run a workgroup-wide solve), so this loops ``act_step`` in Python, one call and at most two
-        launches per step.  ``actions_out``: a contiguous int32 ``[T, A, N]`` tensor (an array on a host env)."""
+        result contract of ``VecQLearning.run``: the tables, the model, every column, the generators and
+        ``solve_info()`` end as the T single steps leave them, bit for bit, and the return sum of the episode
+        statistics agrees to rounding.  On a GPU env the T steps are one launch (rmx_learn_model_run;
+        csrc/rmx_learn_rmax_run.hip, csrc/rmx_learn_qrmax_run.hip): one wave owns one env, lane 0 steps it and
+        applies the model updates, and every solve runs on the wave's 64 lanes at the place the reference has it.  A
+        ``T`` above ``RMX_LEARN_MODEL_RUN_MAX`` is split into consecutive calls; a world whose tables and solve
+        values do not fit in 64 KiB of LDS together is stepped by the same call as T two-launch steps.
+        ``fused=False`` loops ``act_step`` in Python instead, one call and at most two launches per step: the same
+        results.  Measured at config 2 with QRM (profiles/learn_model_run.md): the fused run takes 0.46-0.57 of the
+        loop's time per step at 64 and 4,096 envs and about half on a fresh model at threshold 1 from 4,096 envs up,
+        but at 65,536 envs a step without a solve is 3.0-4.4 times SLOWER fused (a whole wave per env with one lane
+        busy): pass ``fused=False`` there once solves have become rare.  Nothing chooses automatically.
+        ``actions_out``: a contiguous int32 ``[T, A, N]`` tensor (an array on a host env)."""
         env = self.env
         self._epsilon_arg(epsilon)
         T = int(T)
         if T < 1:
             raise ValueError("T must be >= 1")
+        if reference_stream:
+            if self.rng is None:
+                raise RuntimeError("run(reference_stream=True) needs policy_seeds at construction")
+            seed = t_global = 0
+        elif seed is None or t_global is None:
+            raise ValueError("the engine's policy needs seed and t_global")
         AN = env.A * env.N
+        p = flat = None
         if actions_out is not None:
             if self.host:
                 flat = env._out(actions_out, np.int32, T * AN, "actions_out").reshape(-1)
+                p = flat.ctypes.data
             else:
                 t = env.torch
                 if actions_out.dtype is not t.int32 or actions_out.get_device() != env.device.index or \
                         not actions_out.is_contiguous() or actions_out.numel() < T * AN:
                     raise ValueError("actions_out must be a contiguous int32 [T, A, N] tensor on the engine's device")
                 flat = actions_out.view(-1)
-        for k in range(T):
-            self.act_step(None, seed, None if t_global is None else int(t_global) + k, best=best, learn=learn,
-                          actions_out=None if actions_out is None else flat[k * AN:(k + 1) * AN],
-                          reference_stream=reference_stream)
+                p = actions_out.data_ptr()
+        if not fused:
+            for k in range(T):
+                self.act_step(None, seed, int(t_global) + k, best=best, learn=learn,
+                              actions_out=None if flat is None else flat[k * AN:(k + 1) * AN],
+                              reference_stream=reference_stream)
+            return actions_out
+        flags = (_capi.LEARN_UPDATE if learn else 0) | (_capi.LEARN_BEST if best else 0) | \
+            (_capi.LEARN_NUMPY if reference_stream else 0)
+        done = 0
+        while done < T:  # the cap of one launch is invisible from here
+            n = min(T - done, _capi.LEARN_MODEL_RUN_MAX)
+            _capi.check(self.lib.rmx_learn_model_run(env._h, n, flags, int(seed) & (2**64 - 1), int(t_global) + done,
+                                                     None if p is None else p + 4 * done * AN, self._stream()),
+                        "rmx_learn_model_run")
+            done += n
         return actions_out
 
     def _np(self, x):
@@ -521,10 +551,11 @@ class VecQRMax(VecQLearning):
     ``nTSQA``; ``final`` ``[A, N, S_max]`` marks the observed final states; ``q`` starts at ``max_reward * nQ /
     (1 - gamma)`` with ``nQ = enc_nq[a]``, per agent.  An agent-step in which anything became known ends with one
     value iteration (``vi_delta``, ``vi_delta_rel``, at most ``max_iter`` sweeps).  On a GPU env a learn step is the
-    step kernel plus a solve kernel that walks the learners with a solve pending (csrc/rmx_learn_qrmax.hip); a host env
-    runs the same functions in order.  Every table equals the reference's bit for bit, on slip worlds too.
+    step kernel plus a solve kernel that walks the learners with a solve pending (csrc/rmx_learn_qrmax.hip), and
+    ``run(T)`` is one launch in which a wave per env steps and solves in place (csrc/rmx_learn_qrmax_run.hip); a host
+    env runs the same functions in order.  Every table equals the reference's bit for bit, on slip worlds too.
 
-    ``step``, ``act_step``, ``run``, ``greedy`` and the generator accessors are ``VecQLearning``'s.  There is no
+    ``step``, ``act_step``, ``greedy`` and the generator accessors are ``VecQLearning``'s.  There is no
     epsilon: ``act_step`` / ``run`` take none (passing one raises).  With ``reference_stream`` every call shuffles the
     four actions on the learner's generator first, as the reference does; a flat row then picks from the shuffled list,
     any other row takes its first maximum.  ``succ_cap`` (default: ``rmx_learn_qrmax_slots``, which cannot overflow) is
@@ -601,13 +632,14 @@ class VecQRMax(VecQLearning):
         return 0.0
 
     def run(self, T, epsilon=None, seed=None, t_global=None, best=False, learn=True, reference_stream=False,
-            actions_out=None):
-        """``T`` consecutive auto-resetting ``act_step``s (global steps ``t_global .. t_global + T - 1``), with the
-        result contract of ``VecQLearning.run``: the tables, the model, every column and the generators end as the T
-        single steps leave them, because they ARE the T single steps: rmx_learn_run does not serve QR-max (one thread
-        per env cannot run a workgroup-wide solve), so this loops ``act_step`` in Python, one call and at most two
-        launches per step.  ``actions_out``: a contiguous int32 ``[T, A, N]`` tensor (an array on a host env)."""
-        return VecRMax.run(self, T, epsilon, seed, t_global, best, learn, reference_stream, actions_out)
+            actions_out=None, fused=True):
+        """``T`` consecutive auto-resetting ``act_step``s (global steps ``t_global .. t_global + T - 1``) in one
+        launch on a GPU env, exactly as ``VecRMax.run``: the tables, the model, every column, the generators and
+        ``solve_info()`` end as the T single steps leave them, bit for bit.  ``fused=False`` loops ``act_step`` in
+        Python instead: at 65,536 envs with everything known a fused step was measured 2.7 times SLOWER than a looped
+        one (level while learning; 0.32-0.64 of the loop's time at 64 and 4,096 envs; profiles/learn_model_run.md), so
+        pass ``fused=False`` there once solves have become rare.  ``actions_out``: a contiguous int32 ``[T, A, N]`` tensor (an array on a host env)."""
+        return VecRMax.run(self, T, epsilon, seed, t_global, best, learn, reference_stream, actions_out, fused)
 
     def _np(self, x):
         if self.host:
