@@ -311,12 +311,10 @@ uint32_t HostEngine::step_kind(const int32_t* actions, int autoreset, bool hashe
           if (lc->policy == kLearnNumpy) {
             const int64_t plane = (int64_t)A * N;
             uint64_t* w = lc->rng + (int64_t)a * N + e;
-            const uint64_t w4 = w[4 * plane];
-            LearnRng r = {{w[0], w[plane], w[2 * plane], w[3 * plane]}, (uint32_t)(w4 >> 32), (uint32_t)w4};
+            LearnRng r = learn_rng_load(w, plane);
+            const uint64_t w4 = learn_rng_word4(r);
             act[a] = qrmax_policy_numpy(r, lc->best, row[0], row[1], row[2], row[3]);
-            w[0] = r.hi;
-            w[plane] = r.lo;
-            if (learn_rng_word4(r) != w4) w[4 * plane] = learn_rng_word4(r);
+            learn_rng_store(w, plane, r, w4);
           } else {
             act[a] = rmax_policy(seed, t_global, cfg.n_envs_global, cfg.env_offset + e, A, a, lc->best, row[0], row[1],
                                  row[2], row[3]);
@@ -329,12 +327,10 @@ uint32_t HostEngine::step_kind(const int32_t* actions, int autoreset, bool hashe
             if (rmax_row_flat(row[0], row[1], row[2], row[3])) {  // (no draw otherwise: the column is not touched)
               const int64_t plane = (int64_t)A * N;
               uint64_t* w = lc->rng + (int64_t)a * N + e;
-              const uint64_t w4 = w[4 * plane];
-              LearnRng r = {{w[0], w[plane], w[2 * plane], w[3 * plane]}, (uint32_t)(w4 >> 32), (uint32_t)w4};
+              LearnRng r = learn_rng_load(w, plane);
+              const uint64_t w4 = learn_rng_word4(r);
               act[a] = rmax_policy_numpy(r, row[0], row[1], row[2], row[3]);
-              w[0] = r.hi;
-              w[plane] = r.lo;
-              if (learn_rng_word4(r) != w4) w[4 * plane] = learn_rng_word4(r);
+              learn_rng_store(w, plane, r, w4);
             } else {
               act[a] = rmax_argmax(row[0], row[1], row[2], row[3]);
             }
@@ -349,12 +345,10 @@ uint32_t HostEngine::step_kind(const int32_t* actions, int autoreset, bool hashe
         if (lc->policy == kLearnNumpy && !lc->best) {  // the learner's own numpy generator (RMX_LEARN_NUMPY)
           const int64_t plane = (int64_t)A * N;
           uint64_t* w = lc->rng + (int64_t)a * N + e;
-          const uint64_t w4 = w[4 * plane];
-          LearnRng r = {{w[0], w[plane], w[2 * plane], w[3 * plane]}, (uint32_t)(w4 >> 32), (uint32_t)w4};
+          LearnRng r = learn_rng_load(w, plane);
+          const uint64_t w4 = learn_rng_word4(r);
           act[a] = learn_policy_numpy(r, epsilon, row[0], row[1], row[2], row[3]);
-          w[0] = r.hi;
-          w[plane] = r.lo;
-          if (learn_rng_word4(r) != w4) w[4 * plane] = learn_rng_word4(r);
+          learn_rng_store(w, plane, r, w4);
         } else {
           act[a] = learn_policy(seed, t_global, cfg.n_envs_global, cfg.env_offset + e, A, a, epsilon, lc->best,
                                 row[0], row[1], row[2], row[3]);

@@ -5,6 +5,7 @@
 
 #include <cmath>
 #include <string>
+#include <type_traits>
 
 #include "../../include/rmx.h"
 #include "rmx_layout.h"
@@ -362,6 +363,29 @@ struct SyncIO {
 hipError_t launch_resident(const KParams& p, const SyncIO& io, int kind, int threads, size_t lds, hipStream_t st);
 
 inline int amax_bucket(int A) { return A <= 4 ? A : 8; }
+// The learn launchers' ladder over the kernels' leading template arguments (host code): f(KIND, STOCH, AMAX) with
+// std::integral_constant tags for the world kind, rng_on (the handle has slip or random starts: the STOCH
+// instantiations; every other handle runs the kernels it always ran) and amax_bucket(A).  Returns what f returns.
+template <int KIND, bool STOCH, typename F>
+inline auto dispatch_amax(int A, F&& f) {
+  const std::integral_constant<int, KIND> kind;
+  const std::integral_constant<bool, STOCH> stoch;
+  switch (amax_bucket(A)) {
+    case 1: return f(kind, stoch, std::integral_constant<int, 1>());
+    case 2: return f(kind, stoch, std::integral_constant<int, 2>());
+    case 3: return f(kind, stoch, std::integral_constant<int, 3>());
+    case 4: return f(kind, stoch, std::integral_constant<int, 4>());
+    default: return f(kind, stoch, std::integral_constant<int, 8>());
+  }
+}
+template <typename F>
+inline auto dispatch_env(int kind, bool rng_on, int A, F&& f) {
+  if (rng_on)
+    return kind == RMX_FROZEN_LAKE ? dispatch_amax<RMX_FROZEN_LAKE, true>(A, f)
+                                   : dispatch_amax<RMX_OFFICE_WORLD, true>(A, f);
+  return kind == RMX_FROZEN_LAKE ? dispatch_amax<RMX_FROZEN_LAKE, false>(A, f)
+                                 : dispatch_amax<RMX_OFFICE_WORLD, false>(A, f);
+}
 // lanes per env of the lane-per-agent layout: next power of two >= A
 inline int lanes_per_env(int A) { return A <= 1 ? 1 : A <= 2 ? 2 : A <= 4 ? 4 : 8; }
 constexpr int kLayoutThreadPerEnv = 0;

@@ -172,6 +172,21 @@ struct LearnRng : Pcg {  // the generator (rmx_rules.h) and its 32-bit buffer
 // The bound column (rmx_learn_rng_bind): uint64 [5][A][N], word w of learner (a, e) at ((w * A + a) * N + e)
 RMX_HD uint64_t learn_rng_word4(const LearnRng& r) { return ((uint64_t)r.has << 32) | r.u; }
 
+// A learner's round trip over the column, around the policy's draws: w = col + a * N + e, plane = A * N, so the five
+// words are plane-major and each is a coalesced 8-B access per lane.  The load reads all five; the store writes the
+// two state words, and the buffer word only when it changed from w4 = learn_rng_word4 of the loaded generator (the
+// increment never changes).  A policy step that draws nothing calls neither: the column is not touched.
+RMX_HD LearnRng learn_rng_load(const uint64_t* w, int64_t plane) {
+  const uint64_t w4 = w[4 * plane];
+  return {{w[0], w[plane], w[2 * plane], w[3 * plane]}, (uint32_t)(w4 >> 32), (uint32_t)w4};
+}
+RMX_HD void learn_rng_store(uint64_t* w, int64_t plane, const LearnRng& r, uint64_t w4) {
+  w[0] = r.hi;
+  w[plane] = r.lo;
+  const uint64_t n4 = learn_rng_word4(r);
+  if (n4 != w4) w[4 * plane] = n4;
+}
+
 RMX_HD uint32_t learn_pcg_next32(LearnRng& r) {
   if (r.has) {
     r.has = 0;

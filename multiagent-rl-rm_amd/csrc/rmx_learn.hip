@@ -37,6 +37,7 @@
 #include "rmx_generic.h"
 #include "rmx_internal.h"
 #include "rmx_learn.h"
+#include "rmx_learn_body.h"
 
 namespace rmx {
 
@@ -71,11 +72,7 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
     for (int a = 0; a < AMAX; ++a) {
       if (AMAX <= 4 || a < p.A) {
         const int64_t k = (int64_t)a * N + e;
-        s[a].x = p.pos_x[k];
-        s[a].y = p.pos_y[k];
-        s[a].q = p.rm_q[k];
-        s[a].f = p.flags[k];
-        s[a].ret = p.ep_ret[k];
+        load_agent(p, k, s[a]);
         if constexpr (POLICY == kLearnActions) act[a] = p.actions[k];
       }
     }
@@ -120,14 +117,8 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
       if (AMAX <= 4 || a < p.A) {
         q_pre[a] = s[a].q;
         if constexpr (POLICY) {
-          const int64_t S = (int64_t)p.HW * p.enc_nq[a];
-          const int64_t st = ((int64_t)s[a].y * p.W + s[a].x) * p.enc_nq[a] + s[a].q;
-          double2 lo = make_double2(0.0, 0.0), hi = lo;
-          if ((uint64_t)st < (uint64_t)S) {
-            const double2* row = reinterpret_cast<const double2*>(lp.q + (((int64_t)a * N + e) * lp.s_max + st) * 4);
-            lo = row[0];
-            hi = row[1];
-          }
+          double2 lo, hi;
+          policy_row(p, lp, s[a], a, N, e, lo, hi);
           double eps = lc.epsilon;
           if constexpr (EPS)  // (decays under RMX_LEARN_BEST too)
             eps = learn_eps_step(learn_extra<EpsParams>(xp...), a, N, e, was_reset);
@@ -135,16 +126,12 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
             if (lc.best) {  // no draw: the column is not touched
               act[a] = learn_policy(0, 0, 0, 0, p.A, a, eps, 1, lo.x, lo.y, hi.x, hi.y);
             } else {
-              // the learner's five words, plane-major: each a coalesced 8-B load per lane
               const int64_t plane = (int64_t)p.A * N;
               uint64_t* w = lc.rng + (int64_t)a * N + e;
-              const uint64_t w4 = w[4 * plane];
-              LearnRng r = {{w[0], w[plane], w[2 * plane], w[3 * plane]}, (uint32_t)(w4 >> 32), (uint32_t)w4};
+              LearnRng r = learn_rng_load(w, plane);
+              const uint64_t w4 = learn_rng_word4(r);
               act[a] = learn_policy_numpy(r, eps, lo.x, lo.y, hi.x, hi.y);
-              w[0] = r.hi;
-              w[plane] = r.lo;
-              const uint64_t n4 = learn_rng_word4(r);
-              if (n4 != w4) w[4 * plane] = n4;  // (the increment never changes)
+              learn_rng_store(w, plane, r, w4);
             }
           } else {
             act[a] = learn_policy(p.seed, p.t_global, p.n_global, p.env_offset + e, p.A, a, eps, lc.best, lo.x, lo.y,
@@ -166,19 +153,7 @@ __global__ void __launch_bounds__(256) learn_step_kernel(KParams p, LearnParams 
     if (p.env_done) p.env_done[e] = (uint8_t)done;
 #pragma unroll
     for (int a = 0; a < AMAX; ++a) {
-      if (AMAX <= 4 || a < p.A) {
-        const int64_t k = (int64_t)a * N + e;
-        p.pos_x[k] = s[a].x;
-        p.pos_y[k] = s[a].y;
-        p.rm_q[k] = s[a].q;
-        p.flags[k] = s[a].f;
-        p.ep_ret[k] = s[a].ret;
-        p.reward[k] = o[a].reward;
-        if (p.shaping) p.shaping[k] = o[a].shaping;
-        if (p.renv) p.renv[k] = o[a].renv;
-        if (p.enc_state) p.enc_state[k] = enc_index(s[a], p, a);
-        if (p.qrm_s) emit_qrm(o[a], a, e, L, p);
-      }
+      if (AMAX <= 4 || a < p.A) store_agent(p, (int64_t)a * N + e, a, e, s[a], o[a], L);
     }
     // the update: every agent, frozen ones included; an action without a table column (wait, or an invalid one,
     // which the step has reported) has nothing to update
@@ -253,21 +228,9 @@ static hipError_t launch_learn_t(const KParams& p, const LearnParams& lp, const 
   return hipGetLastError();
 }
 
-template <int KIND, bool STOCH>
-static hipError_t launch_learn_k(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
-                                 const EpsParams* eps, dim3 g, dim3 b, size_t lds, hipStream_t st) {
-  switch (amax_bucket(p.A)) {
-    case 1: return launch_learn_t<KIND, 1, STOCH>(p, lp, lc, lam, eps, g, b, lds, st);
-    case 2: return launch_learn_t<KIND, 2, STOCH>(p, lp, lc, lam, eps, g, b, lds, st);
-    case 3: return launch_learn_t<KIND, 3, STOCH>(p, lp, lc, lam, eps, g, b, lds, st);
-    case 4: return launch_learn_t<KIND, 4, STOCH>(p, lp, lc, lam, eps, g, b, lds, st);
-    default: return launch_learn_t<KIND, 8, STOCH>(p, lp, lc, lam, eps, g, b, lds, st);
-  }
-}
-
 // 256-thread blocks, one thread per env (the per-wave statistics slab is sized for that geometry at rmx_create).
 // p.rng_on (the handle has slip or random starts; the caller has checked the learner's dynamics and the rng / episode
-// columns) selects the STOCH instantiations; every other handle runs the kernels it always ran.
+// columns) selects the STOCH instantiations (dispatch_env, rmx_internal.h).
 // lam != NULL: the Q(lambda) kernels.  eps != NULL: the EPS kernels (launch_learn_step_eps, this function as
 // rmx_learn_eps.hip compiles it).
 hipError_t RMX_LAUNCH_LEARN_STEP(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
@@ -276,11 +239,9 @@ hipError_t RMX_LAUNCH_LEARN_STEP(const KParams& p, const LearnParams& lp, const 
   if (eps) return launch_learn_step_eps(p, lp, lc, lam, eps, kind, lds, st);
 #endif
   const dim3 g((unsigned)((p.N + 255) / 256)), b(256);
-  if (p.rng_on)
-    return kind == RMX_FROZEN_LAKE ? launch_learn_k<RMX_FROZEN_LAKE, true>(p, lp, lc, lam, eps, g, b, lds, st)
-                                   : launch_learn_k<RMX_OFFICE_WORLD, true>(p, lp, lc, lam, eps, g, b, lds, st);
-  return kind == RMX_FROZEN_LAKE ? launch_learn_k<RMX_FROZEN_LAKE, false>(p, lp, lc, lam, eps, g, b, lds, st)
-                                 : launch_learn_k<RMX_OFFICE_WORLD, false>(p, lp, lc, lam, eps, g, b, lds, st);
+  return dispatch_env(kind, p.rng_on, p.A, [&](auto K, auto S, auto AM) {
+    return launch_learn_t<K.value, AM.value, S.value>(p, lp, lc, lam, eps, g, b, lds, st);
+  });
 }
 
 #ifndef RMX_LEARN_EPS_TU

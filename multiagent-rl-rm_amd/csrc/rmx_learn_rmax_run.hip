@@ -21,8 +21,8 @@
 // has one slot per 64 envs; the 64 waves of a group add with f64 atomics: the addends are float32 returns, whose
 // float64 sum is exact, and so independent of the order, while their magnitudes span fewer than 29 binary orders).
 // The solve statistics are summed per wave and added once at the end.
-// The step body is rmax_step_kernel's, duplicated as learn_run_kernel duplicates learn_step_kernel's: the existing
-// kernels keep their code.
+// The step body's blocks are the ones rmax_step_kernel calls (rmx_learn_body.h); lane 0 runs them, and the
+// wave-uniform loops around the update are this kernel's own.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -31,6 +31,7 @@
 #include "rmx_generic.h"
 #include "rmx_internal.h"
 #include "rmx_learn.h"
+#include "rmx_learn_body.h"
 #include "rmx_model_solve.h"
 #include "rmx_rmax.h"
 
@@ -56,12 +57,7 @@ __global__ void __launch_bounds__(kRMaxBlock) rmax_run_kernel(KParams p, LearnPa
 #pragma unroll
     for (int a = 0; a < AMAX; ++a) {
       if (AMAX <= 4 || a < p.A) {
-        const int64_t k = (int64_t)a * N + e;
-        s[a].x = p.pos_x[k];
-        s[a].y = p.pos_y[k];
-        s[a].q = p.rm_q[k];
-        s[a].f = p.flags[k];
-        s[a].ret = p.ep_ret[k];
+        load_agent(p, (int64_t)a * N + e, s[a]);
       }
     }
   }
@@ -103,27 +99,18 @@ __global__ void __launch_bounds__(kRMaxBlock) rmax_run_kernel(KParams p, LearnPa
       for (int a = 0; a < AMAX; ++a) {
         if (AMAX <= 4 || a < p.A) {
           q_pre[a] = s[a].q;
-          const int64_t S = (int64_t)p.HW * p.enc_nq[a];
-          const int64_t st = ((int64_t)s[a].y * p.W + s[a].x) * p.enc_nq[a] + s[a].q;
-          double2 lo = make_double2(0.0, 0.0), hi = lo;
-          if ((uint64_t)st < (uint64_t)S) {
-            const double2* row = reinterpret_cast<const double2*>(lp.q + (((int64_t)a * N + e) * lp.s_max + st) * 4);
-            lo = row[0];
-            hi = row[1];
-          }
+          double2 lo, hi;
+          policy_row(p, lp, s[a], a, N, e, lo, hi);
           if constexpr (POLICY == kLearnNumpy) {
             if (lc.best || !rmax_row_flat(lo.x, lo.y, hi.x, hi.y)) {  // no draw: the column is not touched
               act[a] = rmax_argmax(lo.x, lo.y, hi.x, hi.y);
             } else {
               const int64_t plane = (int64_t)p.A * N;
               uint64_t* w = lc.rng + (int64_t)a * N + e;
-              const uint64_t w4 = w[4 * plane];
-              LearnRng r = {{w[0], w[plane], w[2 * plane], w[3 * plane]}, (uint32_t)(w4 >> 32), (uint32_t)w4};
+              LearnRng r = learn_rng_load(w, plane);
+              const uint64_t w4 = learn_rng_word4(r);
               act[a] = rmax_policy_numpy(r, lo.x, lo.y, hi.x, hi.y);
-              w[0] = r.hi;
-              w[plane] = r.lo;
-              const uint64_t n4 = learn_rng_word4(r);
-              if (n4 != w4) w[4 * plane] = n4;
+              learn_rng_store(w, plane, r, w4);
             }
           } else {
             act[a] = rmax_policy(p.seed, p.t_global + it, p.n_global, eg, p.A, a, lc.best, lo.x, lo.y, hi.x, hi.y);
@@ -188,19 +175,7 @@ __global__ void __launch_bounds__(kRMaxBlock) rmax_run_kernel(KParams p, LearnPa
     }
 #pragma unroll
     for (int a = 0; a < AMAX; ++a) {
-      if (AMAX <= 4 || a < p.A) {
-        const int64_t k = (int64_t)a * N + e;
-        p.pos_x[k] = s[a].x;
-        p.pos_y[k] = s[a].y;
-        p.rm_q[k] = s[a].q;
-        p.flags[k] = s[a].f;
-        p.ep_ret[k] = s[a].ret;
-        p.reward[k] = o[a].reward;
-        if (p.shaping) p.shaping[k] = o[a].shaping;
-        if (p.renv) p.renv[k] = o[a].renv;
-        if (p.enc_state) p.enc_state[k] = enc_index(s[a], p, a);
-        if (p.qrm_s) emit_qrm(o[a], a, e, L, p);
-      }
+      if (AMAX <= 4 || a < p.A) store_agent(p, (int64_t)a * N + e, a, e, s[a], o[a], L);
     }
     if (bad) atomicOr(p.err, 1u);
     if (full) atomicOr(p.err, kErrModelFull);
@@ -208,13 +183,7 @@ __global__ void __launch_bounds__(kRMaxBlock) rmax_run_kernel(KParams p, LearnPa
       atomicAdd(wk.stats, solves);
       atomicMax(wk.stats + 1, sweeps_max);
     }
-    if (ls.episodes != 0) {  // the slot of the env's group of 64 (rmx_create sizes the slab by 64 envs per wave)
-      double* slot = p.slab + (size_t)(e >> 6) * RMX_NSTATS;
-      unsafeAtomicAdd(slot + RMX_STAT_SUM_RETURN, ls.ret);
-      unsafeAtomicAdd(slot + RMX_STAT_EPISODES, (double)ls.episodes);
-      unsafeAtomicAdd(slot + RMX_STAT_SUCCESSES, (double)ls.successes);
-      unsafeAtomicAdd(slot + RMX_STAT_SUM_LENGTH, (double)ls.length);
-    }
+    flush_env_stats(p, e, ls);
   }
 }
 
@@ -228,28 +197,14 @@ static hipError_t launch_rmax_run_t(const KParams& p, const LearnParams& lp, con
   return hipGetLastError();
 }
 
-template <int KIND, bool STOCH>
-static hipError_t launch_rmax_run_k(const KParams& p, const LearnParams& lp, const LearnCall& lc, const RMaxParams& rp,
-                                    const RMaxWork& wk, int32_t T, dim3 g, dim3 b, size_t lds, hipStream_t st) {
-  switch (amax_bucket(p.A)) {
-    case 1: return launch_rmax_run_t<KIND, 1, STOCH>(p, lp, lc, rp, wk, T, g, b, lds, st);
-    case 2: return launch_rmax_run_t<KIND, 2, STOCH>(p, lp, lc, rp, wk, T, g, b, lds, st);
-    case 3: return launch_rmax_run_t<KIND, 3, STOCH>(p, lp, lc, rp, wk, T, g, b, lds, st);
-    case 4: return launch_rmax_run_t<KIND, 4, STOCH>(p, lp, lc, rp, wk, T, g, b, lds, st);
-    default: return launch_rmax_run_t<KIND, 8, STOCH>(p, lp, lc, rp, wk, T, g, b, lds, st);
-  }
-}
-
 // One-wave workgroups, workgroup e owns env e.  lds = model_run_lds(tables bytes, s_max) <= kModelRunLdsMax,
 // lc.policy is kLearnHash or kLearnNumpy and 1 <= T (the caller has checked all three).
 hipError_t launch_rmax_run(const KParams& p, const LearnParams& lp, const LearnCall& lc, const RMaxParams& rp,
                            const RMaxWork& wk, int32_t T, int kind, size_t lds, hipStream_t st) {
   const dim3 g((unsigned)p.N), b(kRMaxBlock);
-  if (p.rng_on)
-    return kind == RMX_FROZEN_LAKE ? launch_rmax_run_k<RMX_FROZEN_LAKE, true>(p, lp, lc, rp, wk, T, g, b, lds, st)
-                                   : launch_rmax_run_k<RMX_OFFICE_WORLD, true>(p, lp, lc, rp, wk, T, g, b, lds, st);
-  return kind == RMX_FROZEN_LAKE ? launch_rmax_run_k<RMX_FROZEN_LAKE, false>(p, lp, lc, rp, wk, T, g, b, lds, st)
-                                 : launch_rmax_run_k<RMX_OFFICE_WORLD, false>(p, lp, lc, rp, wk, T, g, b, lds, st);
+  return dispatch_env(kind, p.rng_on, p.A, [&](auto K, auto S, auto AM) {
+    return launch_rmax_run_t<K.value, AM.value, S.value>(p, lp, lc, rp, wk, T, g, b, lds, st);
+  });
 }
 
 }  // namespace rmx

@@ -19,8 +19,10 @@
 // actions_out is stored per step ([T][A][N], a coalesced 4-B store per lane); the episode statistics are summed per
 // lane over the whole run and flushed once per wave, as rollout_kernel's (so the return sum is associated differently
 // from T single steps; the integer statistics are equal).
-// The step body is learn_step_kernel's, duplicated as rollout_kernel duplicates step_kernel's: the existing kernels
-// keep their registers line for line.  The update, the policy and the sweep are rmx_learn.h's.
+// The step body has the same blocks as learn_step_kernel's, written out: the other five learn kernels call
+// rmx_learn_body.h for the blocks they share, but in this kernel each of those calls changed some instantiation's
+// instruction count, so its body stays inline (profiles/learn_body_resources.md).  The update, the policy and the sweep
+// are rmx_learn.h's.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -261,18 +263,6 @@ static hipError_t launch_run_t(const KParams& p, const LearnParams& lp, const Le
   return hipGetLastError();
 }
 
-template <int KIND, bool STOCH>
-static hipError_t launch_run_k(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
-                               const EpsParams* eps, int32_t T, dim3 g, dim3 b, size_t lds, hipStream_t st) {
-  switch (amax_bucket(p.A)) {
-    case 1: return launch_run_t<KIND, 1, STOCH>(p, lp, lc, lam, eps, T, g, b, lds, st);
-    case 2: return launch_run_t<KIND, 2, STOCH>(p, lp, lc, lam, eps, T, g, b, lds, st);
-    case 3: return launch_run_t<KIND, 3, STOCH>(p, lp, lc, lam, eps, T, g, b, lds, st);
-    case 4: return launch_run_t<KIND, 4, STOCH>(p, lp, lc, lam, eps, T, g, b, lds, st);
-    default: return launch_run_t<KIND, 8, STOCH>(p, lp, lc, lam, eps, T, g, b, lds, st);
-  }
-}
-
 // The geometry of launch_learn_step (256-thread blocks, one thread per env: the per-wave statistics slab is sized
 // for it at rmx_create).  lc.policy is kLearnHash or kLearnNumpy and 1 <= T (the caller has checked both).
 hipError_t RMX_LAUNCH_LEARN_RUN(const KParams& p, const LearnParams& lp, const LearnCall& lc, const LambdaParams* lam,
@@ -281,11 +271,9 @@ hipError_t RMX_LAUNCH_LEARN_RUN(const KParams& p, const LearnParams& lp, const L
   if (eps) return launch_learn_run_eps(p, lp, lc, lam, eps, T, kind, lds, st);
 #endif
   const dim3 g((unsigned)((p.N + 255) / 256)), b(256);
-  if (p.rng_on)
-    return kind == RMX_FROZEN_LAKE ? launch_run_k<RMX_FROZEN_LAKE, true>(p, lp, lc, lam, eps, T, g, b, lds, st)
-                                   : launch_run_k<RMX_OFFICE_WORLD, true>(p, lp, lc, lam, eps, T, g, b, lds, st);
-  return kind == RMX_FROZEN_LAKE ? launch_run_k<RMX_FROZEN_LAKE, false>(p, lp, lc, lam, eps, T, g, b, lds, st)
-                                 : launch_run_k<RMX_OFFICE_WORLD, false>(p, lp, lc, lam, eps, T, g, b, lds, st);
+  return dispatch_env(kind, p.rng_on, p.A, [&](auto K, auto S, auto AM) {
+    return launch_run_t<K.value, AM.value, S.value>(p, lp, lc, lam, eps, T, g, b, lds, st);
+  });
 }
 
 }  // namespace rmx

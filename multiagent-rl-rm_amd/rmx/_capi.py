@@ -68,7 +68,7 @@ HASHED_SOURCES = ("rmx_kernels.hip", "rmx_fast.hip", "rmx_fast_step.inc", "rmx_s
                   "rmx_rules.h", "../../include/rmx.h",
                   "Makefile", "rmx_learn_eps.hip", "rmx_learn_run_eps.hip", "rmx_rmax.h", "rmx_learn_rmax.hip",
                   "rmx_qrmax.h", "rmx_learn_qrmax.hip", "rmx_model_solve.h", "rmx_learn_rmax_run.hip",
-                  "rmx_learn_qrmax_run.hip")
+                  "rmx_learn_qrmax_run.hip", "rmx_learn_body.h")
 
 
 def source_hash(csrc: str = CSRC) -> str:
